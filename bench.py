@@ -15,8 +15,12 @@ that are already resident in HBM:
 value = probe rows of all ranks / max-over-ranks time.  The roofline object prices the WHOLE call with the algorithmic
 bytes of SURVEY.md 8d (8*N_p + 8*N_b + 8*N_out; the partition passes count as overhead) and carries the probe phase
 (16 B per probe row over the probe-side launches, live HIP-event timing inside libgdf.so, see csrc/prof.h) and the PMC
-traffic of one join; roofline_kernel prices the dominant kernel on its own contract.  cpu_baseline times oracle/gdf_oracle.c (a
-single-threaded C port of the reference algorithm) on a bounded sample of the same workload.
+traffic of one join; roofline_kernel prices the dominant kernel on its own contract.
+A plain run sets up, warms up, times --steps steps and prints that line.  --full adds what takes runs of its own, after the timed
+region: BASELINE configs C2 / C5, the operators and the shapes next to the headline (extra), the CPU baselines (cpu_baseline: pandas;
+cpu_baseline_oracle_port: oracle/gdf_oracle.c, a single-threaded C port of the reference algorithm, on a bounded sample of the same
+workload; cpu_baseline_all_cores) and, on several GPUs, the planner's own choice (planner_choice).  --dump-outputs DIR writes what the
+last timed step returned (dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -440,6 +444,37 @@ def extra_ops(gdf, dev, n=1_000_000_000, reps=3):
     return out
 
 
+def dump_outputs(gdf, out_dir, li, ri, npr, dev, samples=1 << 21, seed=0x5EED00D0):
+    """--dump-outputs: what the caller of the last timed step received, gdf_inner_join's two index columns, in a form that does not
+    depend on the order the pairs came out in: the build row each probe row joined (-1: none; the build keys are unique, so there is
+    at most one) at a fixed seeded sample of `samples` probe rows.  Writes out_dir/probe_row.npy, build_row.npy (float64: every row
+    number is exact) and pair_count.npy (the length of the index columns), 32 MB in all; releases li and ri."""
+    import numpy as np
+    import torch
+    from libgdf_amd import libgdf
+    n = int(li.size)
+    l = torch.empty(n, dtype=torch.int32, device=dev)
+    r = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        gdf.api._hipMemcpyDtoD(l.data_ptr(), li.data, n * 4)
+        gdf.api._hipMemcpyDtoD(r.data_ptr(), ri.data, n * 4)
+    libgdf.gdf_column_free(C.byref(li))
+    libgdf.gdf_column_free(C.byref(ri))
+    if n and not (int(l.min()) >= 0 and int(l.max()) < npr):
+        raise RuntimeError(f"--dump-outputs: a left index outside [0, {npr})")
+    match = torch.full((npr,), -1, dtype=torch.int32, device=dev)
+    match[l.long()] = r
+    del l, r
+    rows = np.unique(np.random.RandomState(seed).randint(0, npr, size=samples)) if npr > samples else np.arange(npr)
+    build_row = match[torch.from_numpy(rows).to(dev)].cpu().numpy()
+    del match
+    torch.cuda.empty_cache()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "probe_row.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "build_row.npy"), build_row.astype(np.float64))
+    np.save(os.path.join(out_dir, "pair_count.npy"), np.array([n], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -453,21 +488,31 @@ def main():
                     help="A/B switch: challengers the pool draws per placed scratch block (library default 4; 0 = never re-draw)")
     ap.add_argument("--probe-rows", type=int, default=1_000_000_000)
     ap.add_argument("--build-rows", type=int, default=None)
-    ap.add_argument("--cpu-sample", type=int, default=20_000_000, help="probe rows of the oracle-port CPU baseline sample (0 = skip)")
-    ap.add_argument("--pandas-sample", type=int, default=100_000_000, help="probe rows of the pandas.merge CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=20_000_000, help="with --full: probe rows of the oracle-port CPU baseline sample (0 = skip)")
+    ap.add_argument("--pandas-sample", type=int, default=100_000_000, help="with --full: probe rows of the pandas.merge CPU baseline (0 = skip)")
     ap.add_argument("--strategy", choices=["exchange", "auto", "fused", "shuffle", "broadcast"], default="exchange",
                     help="multi-GPU join.  exchange (default): the key-partitioned all-to-all join BASELINE.json names, at EVERY world size -- "
                          "the fused variant (rank split in the join's level-1 regroup, 4-byte keys in fixed-size blocks) and, where the shape does "
                          "not fit it, the plain key shuffle -- so that a 1 -> 8 GPU curve measures one algorithm; what the planner "
                          "(libgdf_amd.multigpu.choose_join_strategy: broadcast at 2 GPUs, shuffle at 4, fused at 8) would have run instead is timed "
-                         "after it and reported in the extra field planner_choice.  auto: the planner's choice as `value`.  fused / shuffle / "
+                         "after it (with --full) and reported in the extra field planner_choice.  auto: the planner's choice as `value`.  fused / shuffle / "
                          "broadcast: that strategy")
     ap.add_argument("--extra", type=int, default=1,
-                    help="1 (default, single GPU only): after the headline's timed region, also measure BASELINE configs C2 and C5 through the C ABI "
-                         "and append them as `extra.c2` / `extra.c5` (ms, roofline fraction, checks_pass); 0 = skip")
+                    help="with --full, 1 (default, single GPU only): after the headline's timed region, also measure BASELINE configs C2 and C5 "
+                         "through the C ABI and append them as `extra.c2` / `extra.c5` (ms, roofline fraction, checks_pass); 0 = skip")
     ap.add_argument("--force-distributed", action="store_true",
                     help="run the multi-GPU (C4) code path even at world size 1 (1-rank RCCL group): measures its local passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the extra configs, operators and shapes (--extra), the "
+                         "CPU baselines (--pandas-sample, --cpu-sample) and, on several GPUs, the planner's choice.  Off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/*.npy (float64, a fixed seeded sample: dump_outputs); "
+                         "single-GPU path only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and (args.gpus > 1 or args.force_distributed):
+        ap.error("--dump-outputs: the single-GPU path only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run, exactly
@@ -525,11 +570,13 @@ def main():
         la, ra = column_array([pcol]), column_array([bcol])
         on = (C.c_int * 1)(0)
 
-        def step():
-            # exactly one C-ABI call; the library-allocated index columns are released, not copied
+        def step(keep=False):
+            # exactly one C-ABI call; the library-allocated index columns are released, not copied (keep: handed back instead)
             li, ri = gdf_column(), gdf_column()
             libgdf.gdf_inner_join(la, 1, on, ra, 1, on, 1, 0, None, C.byref(li), C.byref(ri), C.byref(ctx))
             n = int(li.size)
+            if keep:
+                return n, (li, ri)
             libgdf.gdf_column_free(C.byref(li))
             libgdf.gdf_column_free(C.byref(ri))
             return n
@@ -649,9 +696,13 @@ def main():
     lib.gdf_amd_profile_reset()
     lib.gdf_amd_profile_enable(1)
     sync()
+    kept = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out_rows = step()
+    for i in range(args.steps):
+        if args.dump_outputs is not None and i == args.steps - 1:
+            out_rows, kept = step(keep=True)       # the last step's index columns, for --dump-outputs (released after the timed region)
+        else:
+            out_rows = step()
     sync()
     dt = time.perf_counter() - t0
     lib.gdf_amd_profile_enable(0)
@@ -660,10 +711,13 @@ def main():
     for k_, v_ in prof_sides.items():
         a_, b_ = prof.get(k_.split("@")[0], (0.0, 0))
         prof[k_.split("@")[0]] = (a_ + v_[0], b_ + v_[1])
+    if kept is not None:
+        dump_outputs(gdf, args.dump_outputs, kept[0], kept[1], npr, dev)
+        kept = None
 
     # what the planner would have run at this world size, when that is another strategy than the one `value` reports
     planner_choice = None
-    if distributed and args.strategy == "exchange" and planner != strategy:
+    if args.full and distributed and args.strategy == "exchange" and planner != strategy:
         pstep = steps[planner][0]
         err = None
         try:
@@ -793,7 +847,7 @@ def main():
                                   "assumed_link_GBps": multigpu.XGMI_LINK_BYTES_PER_S / 1e9,
                                   "planner_estimate_ms": {k: v * 1e3 for k, v in multigpu.estimate_join_seconds(world, npr, nb).items()}}
             result["per_rank"] = per_rank
-        if world == 1 and not distributed and args.extra and npr == 1_000_000_000:
+        if args.full and world == 1 and not distributed and args.extra and npr == 1_000_000_000:
             # the other two single-GPU BASELINE configs, measured AFTER the headline's timed region with its inputs released
             # (a driver-run line, not only profiles/, carries them)
             step = pcol = bcol = la = ra = probe = build = None      # (the step closure holds the columns)
@@ -805,9 +859,9 @@ def main():
                 result["extra"]["shapes"] = extra_shapes(gdf, dev, ms_per_step)
             except Exception as e:                 # noqa: BLE001 -- an extra, never fatal for the headline line
                 result["extra"]["shapes"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.pandas_sample > 0:
+        if args.full and world == 1 and args.pandas_sample > 0:
             result["cpu_baseline"] = cpu_baseline_pandas(args.pandas_sample, max(args.pandas_sample // 10, 1))
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             port = cpu_baseline(args.cpu_sample, max(args.cpu_sample // 10, 1))
             result["cpu_baseline_oracle_port"] = port
             result.setdefault("cpu_baseline", port)

@@ -9,6 +9,7 @@ host.  The JSON holds data only (values and their hashes).
 import ctypes as C
 import json
 import os
+import sys
 
 import numpy as np
 
@@ -57,6 +58,21 @@ def main():
     with open(os.path.join(HERE, "murmur3_32.json"), "w") as f:
         json.dump(out, f, indent=1)
     print("wrote murmur3_32.json")
+
+    # the reference's answers on the seeded inputs of tests/test_oracle_pinning.py::test_against_live_reference_header
+    sys.path[:0] = [os.path.join(HERE, "..", ".."), os.path.join(HERE, "..")]
+    from test_oracle_pinning import sampled_hash_inputs
+    vals, pairs = sampled_hash_inputs()
+    sampled = {"source": "reference src/hashmap/hash_functions.cuh via oracle/ref_hash_shim.cpp, on "
+                         "tests/test_oracle_pinning.py:sampled_hash_inputs()", "murmur3_32": {}}
+    for name, v in vals.items():
+        fn = getattr(ref, "ref_murmur_" + name)
+        sampled["murmur3_32"][name] = [int(fn(v[i:i + 1].ctypes.data)) for i in range(len(v))]
+    sampled["hash_combine"] = [int(ref.ref_hash_combine(int(l), int(r))) for l, r in pairs]
+    with open(os.path.join(HERE, "murmur3_32_sampled.json"), "w") as f:
+        json.dump(sampled, f)
+        f.write("\n")
+    print("wrote murmur3_32_sampled.json")
 
 
 if __name__ == "__main__":

@@ -1,6 +1,8 @@
 """No-GPU checks of the drop-in boundary: the libraries load, export every symbol include/gdf/gdf.h and
 include/memory.h declare, and the struct layouts are the reference's."""
 import ctypes as C
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -66,17 +68,30 @@ def test_librmm_exports_every_declared_symbol(libs):
     assert not missing, missing
 
 
-def test_reference_function_list_is_covered(libs):
-    """Every function name the reference's cffi headers declare is exported (only when /root/reference is present)."""
-    gdf, _ = libs
-    ref = "/root/reference/libgdf/include/gdf/cffi"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present on this machine")
-    text = open(os.path.join(ref, "functions.h")).read() + open(os.path.join(ref, "io_functions.h")).read()
+GOLDEN_ABI = os.path.join(ROOT, "tests", "golden", "reference_abi.json")
+
+
+@pytest.fixture(scope="module")
+def reference_abi():
+    """What the reference's cffi headers declare, recorded by tests/golden/make_abi_golden.py: the function names, a digest of every
+    prototype (return and parameter types) and the layout / enumerator table the program below prints when built against them."""
+    with open(GOLDEN_ABI) as f:
+        return json.load(f)
+
+
+def reference_function_names(cffi_dir):
+    """Every function name functions.h and io_functions.h of a cffi header directory declare."""
+    text = open(os.path.join(cffi_dir, "functions.h")).read() + open(os.path.join(cffi_dir, "io_functions.h")).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
     text = re.sub(r"\s+", " ", text)
-    names = set(re.findall(r"\b((?:gdf|gpu)_[A-Za-z0-9_]+|read_csv|get_column_byte_width) ?\(", text))
+    return set(re.findall(r"\b((?:gdf|gpu)_[A-Za-z0-9_]+|read_csv|get_column_byte_width) ?\(", text))
+
+
+def test_reference_function_list_is_covered(libs, reference_abi):
+    """Every function name the reference's cffi headers declare is exported."""
+    gdf, _ = libs
+    names = set(reference_abi["functions"])
     assert len(names) > 280
     missing = [n for n in sorted(names) if not hasattr(gdf, n)]
     assert not missing, missing
@@ -119,13 +134,8 @@ def _prototypes(header, include_dirs):
     return out
 
 
-def test_reference_prototypes_match_type_for_type():
-    """VERDICT r4 item 8: not only the NAMES -- return type and every parameter type of every function the reference's cffi headers
-    declare (include/gdf/cffi/functions.h:1-785, io_functions.h, with types.h / io_types.h / convert_types.h for the typedefs) must be
-    what include/gdf/gdf.h declares.  Both sides go through `gcc -E`; skipped where the reference tree is absent (the GPU box)."""
-    ref_inc = "/root/reference/libgdf/include"
-    if not os.path.isdir(os.path.join(ref_inc, "gdf", "cffi")):
-        pytest.skip("reference tree not present on this machine")
+def reference_prototypes(ref_inc):
+    """_prototypes of the reference's five cffi headers (under ref_inc/gdf/cffi), restricted to the library's functions."""
     import tempfile
     with tempfile.TemporaryDirectory() as d:
         # the reference's gdf.h is C++; its five cffi headers are plain C, read in the order libgdf_cffi/libgdf_build.py:6 cdefs them
@@ -133,23 +143,30 @@ def test_reference_prototypes_match_type_for_type():
         open(tu, "w").write("#include <stddef.h>\n#include <stdint.h>\n#include <stdbool.h>\n" + "".join(
             f'#include "gdf/cffi/{h}"\n' for h in ("types.h", "convert_types.h", "functions.h", "io_types.h", "io_functions.h")))
         ref = _prototypes(tu, [ref_inc])
+    return {k: v for k, v in ref.items() if re.match(r"(gdf|gpu)_|read_csv$|get_column_byte_width$", k)}
+
+
+def prototype_digest(ret, params):
+    """sha256 (first 16 hex digits) of one normalised prototype from _prototypes: what tests/golden/reference_abi.json records per
+    function instead of the declaration itself."""
+    return hashlib.sha256(f"{ret} ({', '.join(params)})".encode()).hexdigest()[:16]
+
+
+def test_reference_prototypes_match_type_for_type(reference_abi):
+    """VERDICT r4 item 8: not only the NAMES -- return type and every parameter type of every function the reference's cffi headers
+    declare (include/gdf/cffi/functions.h:1-785, io_functions.h, with types.h / io_types.h / convert_types.h for the typedefs) must be
+    what include/gdf/gdf.h declares.  Both sides went through `gcc -E` and _prototypes; the reference's side is recorded as one
+    prototype_digest per function in tests/golden/reference_abi.json."""
+    ref = reference_abi["prototype_sha256"]
     ours = _prototypes(os.path.join(ROOT, "include", "gdf", "gdf.h"), [os.path.join(ROOT, "include")])
-    ref = {k: v for k, v in ref.items() if re.match(r"(gdf|gpu)_|read_csv$|get_column_byte_width$", k)}
     assert len(ref) > 280, len(ref)
     missing = sorted(set(ref) - set(ours))
     assert not missing, missing
-    different = {k: (ref[k], ours[k]) for k in ref if ref[k] != ours[k]}
+    different = {k: ours[k] for k in ref if prototype_digest(*ours[k]) != ref[k]}
     assert not different, different
 
 
-def test_reference_struct_and_enum_definitions_match():
-    """gdf_column / gdf_context member types and order, and every enumerator's VALUE (types.h:15-195), against the reference's own
-    headers: both compiled by gcc into a table of offsets / sizes / values and compared."""
-    ref_inc = "/root/reference/libgdf/include"
-    if not os.path.isdir(os.path.join(ref_inc, "gdf", "cffi")):
-        pytest.skip("reference tree not present on this machine")
-    import tempfile
-    prog = r"""
+_LAYOUT_PROGRAM = r"""
 #include <stdio.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -179,14 +196,24 @@ int main(void) {
   return 0;
 }
 """
-    outs = []
+
+
+def layout_table(inc, ref=False):
+    """gdf_column / gdf_context member offsets and sizes and every enumerator's value, as printed by _LAYOUT_PROGRAM compiled by gcc
+    against the headers under inc (ref=True: a reference include directory with gdf/cffi/*.h)."""
+    import tempfile
     with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "t.c"), "w").write(prog)
-        for inc in (ref_inc, os.path.join(ROOT, "include")):
-            exe = os.path.join(d, "t")
-            subprocess.check_call(["gcc", "-I", inc, *(["-DREF"] if inc == ref_inc else []), os.path.join(d, "t.c"), "-o", exe])
-            outs.append(subprocess.check_output([exe]).decode())
-    assert outs[0] == outs[1], outs
+        open(os.path.join(d, "t.c"), "w").write(_LAYOUT_PROGRAM)
+        exe = os.path.join(d, "t")
+        subprocess.check_call(["gcc", "-I", inc, *(["-DREF"] if ref else []), os.path.join(d, "t.c"), "-o", exe])
+        return subprocess.check_output([exe]).decode()
+
+
+def test_reference_struct_and_enum_definitions_match(reference_abi):
+    """gdf_column / gdf_context member types and order, and every enumerator's VALUE (types.h:15-195), against the reference's own
+    headers: both compiled by gcc into a table of offsets / sizes / values and compared (the reference's table is recorded in
+    tests/golden/reference_abi.json)."""
+    assert layout_table(os.path.join(ROOT, "include")) == reference_abi["layout"]
 
 
 def test_struct_layout(libs):

@@ -55,3 +55,16 @@ def test_committed_pmc_summary_matches_this_build():
     if traffic is None:
         pytest.skip(f"no PMC summary for build {bench.library_build_id()}: {src}")
     assert 3.0e10 < traffic < 6.0e10, (traffic, src)          # one C3 join moves ~46 GB
+
+
+def test_bad_steps_and_dump_outputs_are_refused_before_any_work(monkeypatch):
+    """--steps sets the number of timed steps (at least one); --dump-outputs writes the single-GPU join's result only."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(os, "execv", lambda *a: pytest.fail("must not launch ranks"))
+    for argv in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "d"], ["--force-distributed", "--dump-outputs", "d"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2, argv

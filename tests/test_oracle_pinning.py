@@ -1,7 +1,7 @@
 """Pins the CPU oracle before anything is compared against it (no GPU needed):
   * Murmur3_32 / hash_combine / IdentityHash against golden vectors captured from the reference's own
-    header (tests/golden/murmur3_32.json, made by tests/golden/make_golden.py), and -- when the build
-    container's oracle/_ref/libref_hash.so is present -- against the reference functors live;
+    header (tests/golden/murmur3_32.json and murmur3_32_sampled.json, made by tests/golden/make_golden.py), and
+    -- where oracle/_ref/libref_hash.so was built -- against the reference functors live;
   * group-by and filter semantics against the known-answer vectors of the reference's sqls tests
     (tests/golden/sqls_known_answers.json);
   * the numpy expectations against the statements in the reference's python tests."""
@@ -61,23 +61,41 @@ def test_hash_combine_and_identity_golden(golden):
         assert oracle.identity_hash(np.int32(e["v"])) == e["out"]
 
 
+def sampled_hash_inputs():
+    """The seeded inputs of test_against_live_reference_header: 500 values of every dtype made of random bytes, then 500 hash_combine
+    pairs (tests/golden/make_golden.py records the reference functors' answers on exactly these)."""
+    rng = np.random.RandomState(7)
+    vals = {}
+    for name, dt in NP.items():
+        raw = rng.randint(0, 256, size=(500, np.dtype(dt).itemsize), dtype=np.uint8)
+        vals[name] = raw.view(dt).reshape(-1)
+    pairs = rng.randint(0, 2**32, size=(500, 2), dtype=np.int64)
+    return vals, pairs
+
+
 def test_against_live_reference_header():
+    """The oracle against the reference's own functors on 3,500 seeded inputs: their answers as recorded from the reference header
+    (tests/golden/murmur3_32_sampled.json), and live as well where oracle/_ref/libref_hash.so was built."""
+    vals, pairs = sampled_hash_inputs()
+    with open(os.path.join(GOLD, "murmur3_32_sampled.json")) as f:
+        rec = json.load(f)
+    for name, v in vals.items():
+        assert [oracle.murmur3_32(v[i:i + 1]) for i in range(len(v))] == rec["murmur3_32"][name], name
+    assert [oracle.hash_combine(int(l), int(r)) for l, r in pairs] == rec["hash_combine"]
     path = os.path.join(HERE, "..", "oracle", "_ref", "libref_hash.so")
     if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+        return
     ref = C.CDLL(path)
-    rng = np.random.RandomState(7)
     for name, dt in NP.items():
         fn = getattr(ref, "ref_murmur_" + name)
         fn.restype = C.c_uint32
         fn.argtypes = [C.c_void_p]
-        raw = rng.randint(0, 256, size=(500, np.dtype(dt).itemsize), dtype=np.uint8)
-        vals = raw.view(dt).reshape(-1)
-        for i in range(len(vals)):
-            assert oracle.murmur3_32(vals[i:i + 1]) == fn(vals[i:i + 1].ctypes.data)
+        v = vals[name]
+        for i in range(len(v)):
+            assert oracle.murmur3_32(v[i:i + 1]) == fn(v[i:i + 1].ctypes.data)
     ref.ref_hash_combine.restype = C.c_uint32
     ref.ref_hash_combine.argtypes = [C.c_uint32, C.c_uint32]
-    for l, r in rng.randint(0, 2**32, size=(500, 2), dtype=np.int64):
+    for l, r in pairs:
         assert oracle.hash_combine(int(l), int(r)) == ref.ref_hash_combine(int(l), int(r))
 
 

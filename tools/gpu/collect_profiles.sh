@@ -7,7 +7,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
 timeout 3000 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" > $O/pytest_gpu.txt
-python bench.py 2>$O/bench.err | grep '^{' | tail -1 > $O/bench.json
+python bench.py --full 2>$O/bench.err | grep '^{' | tail -1 > $O/bench.json
 python tools/bench_ops.py > $O/bench_ops.jsonl 2>/dev/null
 python tools/bench_c5.py 2>/dev/null | tail -1 > $O/bench_c5.json
 python tools/bench_shapes.py > $O/bench_shapes.jsonl 2>/dev/null

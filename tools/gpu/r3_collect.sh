@@ -16,7 +16,7 @@ cd $R
 python tools/rocprof_summary.py $O/trace $O/kernel_stats.md
 python tools/pmc_hbm_json.py $(find $O/pmc_fetch -name "*counter_collection.csv" | head -1) $(find $O/pmc_write -name "*counter_collection.csv" | head -1) $O/pmc_hbm.json
 cp $O/pmc_hbm.json $R/profiles/zz_tmp_pmc_hbm.json          # so that THIS run's bench line already carries the traffic
-python bench.py 2>$O/bench.err | grep '^{' | tail -1 > $O/bench.json
+python bench.py --full 2>$O/bench.err | grep '^{' | tail -1 > $O/bench.json
 rm -f $R/profiles/zz_tmp_pmc_hbm.json
 for i in 1 2 3; do python bench.py --steps 10 --warmup 3 --cpu-sample 0 --pandas-sample 0 2>/dev/null | grep '^{' | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({'ms_per_step': d['ms_per_step'], 'kernels_ms_per_step': d['kernels_ms_per_step']}))" >> $O/bench_spread.jsonl; done
 python tools/bench_c5.py 2>/dev/null | tail -1 > $O/bench_c5.json

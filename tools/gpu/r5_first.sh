@@ -13,5 +13,5 @@ done
 cat $O/place_ab.jsonl | cut -c1-400
 python tools/gpu/r5_place.py 4 > $O/place_trace_4.json 2>$O/place_trace_4.err; tail -c 3000 $O/place_trace_4.json
 python tools/gpu/r5_place.py 4 > $O/place_trace_4b.json 2>/dev/null
-python bench.py --steps 5 --warmup 6 > $O/bench_full.json 2>$O/bench_full.err; cut -c1-1500 $O/bench_full.json
+python bench.py --full --steps 5 --warmup 6 > $O/bench_full.json 2>$O/bench_full.err; cut -c1-1500 $O/bench_full.json
 timeout 2400 python -m pytest tests -m gpu -q -x --durations=120 > $O/pytest_gpu.txt 2>&1; tail -140 $O/pytest_gpu.txt
