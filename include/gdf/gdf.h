@@ -259,13 +259,81 @@ gdf_error gpu_apply_stencil(gdf_column *lhs, gdf_column *stencil, gdf_column *ou
 gdf_error gdf_filter(size_t nrows, gdf_column *cols, size_t ncols, void **d_cols, int *d_types,
                      void **d_vals, size_t *d_indx, size_t *new_sz);
 
+/* --- whole-column reductions (functions.h:692-705 and the gdf_sum_ family; reference src/reductions.cu): csrc/reduce.hip
+ *
+ * The result goes to dev_result[0] (DEVICE memory) in the column's own type; nothing else of dev_result is written (the
+ * partials live in library scratch).  Any dev_result_size >= 1 works and the result does not depend on it;
+ * gdf_reduce_optimal_output_size() returns the reference's 128 because callers size their buffers from it.
+ *   errors     NULL col / dev_result or dev_result_size < 1: GDF_INVALID_API_CALL, before any device work.
+ *              _generic: sum / product / min / max take INT8, INT32, INT64, FLOAT32, FLOAT64; sum_squared FLOAT32 and
+ *              FLOAT64 only; anything else GDF_UNSUPPORTED_DTYPE.  A typed entry point takes a column of its own storage
+ *              (_i32: INT32 / DATE32, _i64: INT64 / DATE64 / TIMESTAMP) and answers GDF_DTYPE_MISMATCH otherwise (the
+ *              reference would reinterpret the bytes).
+ *   nulls      a null row contributes the identity; an empty or all-null column gives the identity: 0 for sum and
+ *              sum_squared, 1 for product, numeric_limits<T>::max() for min and ::lowest() for max (for floats
+ *              +-FLT_MAX / +-DBL_MAX, not +-inf, as in the reference; the identity takes part in every result).
+ *   integers   accumulate and wrap in the input type (an int8 sum is mod 2^8, an int32 product mod 2^32).
+ *   floats     f32 sum and sum_squared accumulate in f64 and round once at the end; product, min and max work in the input
+ *              type; min and max return NaN when a valid element is NaN (numpy's np.min / np.max).
+ *   determinism  the grid and the combine order are fixed: the same input on the same device gives a bit-identical result.
+ *   stream     the legacy default stream; the call returns after the result is written.                                    */
+unsigned int gdf_reduce_optimal_output_size(void);
+gdf_error gdf_sum_generic(gdf_column *col, void *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_sum_f64(gdf_column *col, double *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_sum_f32(gdf_column *col, float *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_sum_i64(gdf_column *col, int64_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_sum_i32(gdf_column *col, int32_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_sum_i8(gdf_column *col, int8_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_product_generic(gdf_column *col, void *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_product_f64(gdf_column *col, double *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_product_f32(gdf_column *col, float *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_product_i64(gdf_column *col, int64_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_product_i32(gdf_column *col, int32_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_product_i8(gdf_column *col, int8_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_min_generic(gdf_column *col, void *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_min_f64(gdf_column *col, double *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_min_f32(gdf_column *col, float *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_min_i64(gdf_column *col, int64_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_min_i32(gdf_column *col, int32_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_min_i8(gdf_column *col, int8_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_max_generic(gdf_column *col, void *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_max_f64(gdf_column *col, double *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_max_f32(gdf_column *col, float *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_max_i64(gdf_column *col, int64_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_max_i32(gdf_column *col, int32_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_max_i8(gdf_column *col, int8_t *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_sum_squared_generic(gdf_column *col, void *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_sum_squared_f64(gdf_column *col, double *dev_result, gdf_size_type dev_result_size);
+gdf_error gdf_sum_squared_f32(gdf_column *col, float *dev_result, gdf_size_type dev_result_size);
+
+/* --- quantiles (functions.h:774-785; reference src/quantiles.cu): csrc/quantile.hip
+ *
+ * Let n be the column size and s the column in ascending order, NaN last.
+ *   errors     a validity mask: GDF_VALIDITY_UNSUPPORTED (as the reference).  n == 0: GDF_DATASET_EMPTY.  NULL col, result
+ *              pointer or ctxt, q NaN or q < 0: GDF_INVALID_API_CALL.  prec outside gdf_quantile_method:
+ *              GDF_UNSUPPORTED_METHOD.  Dtypes INT8, INT16, INT32, INT64, FLOAT32, FLOAT64; anything else
+ *              GDF_UNSUPPORTED_DTYPE.
+ *   rule       q >= 1 gives s[n-1] (the max) and n == 1 gives s[0], for every method.  Otherwise pos = q * n (double),
+ *              k = floor(pos), x = pos - k, and then k is decreased by one if it is positive (x is taken BEFORE that
+ *              decrement, as in the reference).  y0 = s[k], y1 = s[k+1].
+ *   results    gdf_quantile_aprrox writes y0 as a T to the HOST pointer t_erased_res.  gdf_quantile_exact writes a double
+ *              to the host pointer: LINEAR y0 + x * (y1 - y0), LOWER y0, HIGHER y1, MIDPOINT (y0 + y1) / 2.0,
+ *              NEAREST x < 0.5 ? y0 : y1.  y1 - y0 and y0 + y1 are computed in the column type under C promotion
+ *              before the conversion to double: int8 and int16 promote to int, int32 and int64 wrap in two's
+ *              complement, float stays float.
+ *   modes      ctxt->flag_sorted: the column is trusted to be sorted and is read, not modified.
+ *              ctxt->flag_sort_inplace (and not sorted): the column is left sorted ascending (NaN last).
+ *              neither: the column is neither modified nor copied (radix selection).
+ *              A zero's sign in a result is that of some zero of the column.                                            */
+gdf_error gdf_quantile_exact(gdf_column *col_in, gdf_quantile_method prec, double q, void *t_erased_res, gdf_context *ctxt);
+gdf_error gdf_quantile_aprrox(gdf_column *col_in, double q, void *t_erased_res, gdf_context *ctxt);
+
 /* ======================================================================== *
  *  Out-of-scope entry points: exported, return GDF_UNSUPPORTED_METHOD.     *
  * ======================================================================== */
 #define GDF_DECL_UNARY(name)        gdf_error name(gdf_column *input, gdf_column *output);
 #define GDF_DECL_UNARY_TU(name)     gdf_error name(gdf_column *input, gdf_column *output, gdf_time_unit time_unit);
 #define GDF_DECL_BINARY(name)       gdf_error name(gdf_column *lhs, gdf_column *rhs, gdf_column *output);
-#define GDF_DECL_REDUCE(name, T)    gdf_error name(gdf_column *col, T *dev_result, gdf_size_type dev_result_size);
 #define GDF_DECL_RSORT(name)        gdf_error name(gdf_radixsort_plan_type *hdl, gdf_column *keycol, gdf_column *valcol);
 #define GDF_DECL_SEGSORT(name)      gdf_error name(gdf_segmented_radixsort_plan_type *hdl, gdf_column *keycol, gdf_column *valcol, \
                                                    unsigned num_segments, unsigned *d_begin_offsets, unsigned *d_end_offsets);
@@ -273,7 +341,6 @@ gdf_error gdf_filter(size_t nrows, gdf_column *cols, size_t ncols, void **d_cols
 #undef GDF_DECL_UNARY
 #undef GDF_DECL_UNARY_TU
 #undef GDF_DECL_BINARY
-#undef GDF_DECL_REDUCE
 #undef GDF_DECL_RSORT
 #undef GDF_DECL_SEGSORT
 
@@ -307,12 +374,9 @@ gdf_error   gdf_radixsort_plan_free(gdf_radixsort_plan_type *hdl);
 gdf_segmented_radixsort_plan_type *gdf_segmented_radixsort_plan(size_t num_items, int descending, unsigned begin_bit, unsigned end_bit);
 gdf_error   gdf_segmented_radixsort_plan_setup(gdf_segmented_radixsort_plan_type *hdl, size_t sizeof_key, size_t sizeof_val);
 gdf_error   gdf_segmented_radixsort_plan_free(gdf_segmented_radixsort_plan_type *hdl);
-unsigned int gdf_reduce_optimal_output_size(void);
 gdf_error   gpu_concat(gdf_column *lhs, gdf_column *rhs, gdf_column *output);
 gdf_error   gpu_hash_columns(gdf_column **columns_to_hash, int num_columns, gdf_column *output_column, void *stream);
 gdf_error   gdf_order_by(size_t nrows, gdf_column *cols, size_t ncols, void **d_cols, int *d_types, size_t *d_indx);
-gdf_error   gdf_quantile_exact(gdf_column *col_in, gdf_quantile_method prec, double q, void *t_erased_res, gdf_context *ctxt);
-gdf_error   gdf_quantile_aprrox(gdf_column *col_in, double q, void *t_erased_res, gdf_context *ctxt);
 gdf_error   read_csv(csv_read_arg *args);
 gdf_error   gdf_to_csr(gdf_column **gdfData, int num_cols, csr_gdf *csrReturn);
 

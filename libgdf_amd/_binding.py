@@ -145,7 +145,16 @@ _PROTOTYPES = {
     "gdf_order_by": (None, [C.c_size_t, _COLP, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdf_filter": (None, [C.c_size_t, _COLP, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.POINTER(C.c_size_t)]),
+    # whole-column reductions (csrc/reduce.hip): the result pointer is a DEVICE address, passed as an integer
+    "gdf_reduce_optimal_output_size": (C.c_uint, []),
+    # quantiles (csrc/quantile.hip): q is a C double -- without c_double in argtypes ctypes would pass an int; the result is a
+    # HOST pointer (a double for exact, a T for approx)
+    "gdf_quantile_exact": (None, [_COLP, C.c_int, C.c_double, C.c_void_p, _CTXP]),
+    "gdf_quantile_aprrox": (None, [_COLP, C.c_double, C.c_void_p, _CTXP]),
 }
+for _op in ("sum", "product", "min", "max", "sum_squared"):
+    for _sfx in (("generic", "f64", "f32") if _op == "sum_squared" else ("generic", "f64", "f32", "i64", "i32", "i8")):
+        _PROTOTYPES[f"gdf_{_op}_{_sfx}"] = (None, [_COLP, C.c_void_p, C.c_size_t])
 
 _RMM_PROTOTYPES = {
     "rmmInitialize": (None, [C.POINTER(rmmOptions_t)]),

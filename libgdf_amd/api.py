@@ -340,6 +340,37 @@ def prefixsum(col: Column, inclusive=True):
     return out.data
 
 
+REDUCE_OPS = ("sum", "product", "min", "max", "sum_squared")
+QUANTILE_METHODS = {"linear": 0, "lower": 1, "higher": 2, "midpoint": 3, "nearest": 4}
+
+
+def reduce(op: str, col: Column):
+    """gdf_<op>_generic: a numpy scalar of the column's dtype (the library writes it to device memory; this reads it back)."""
+    import torch
+    if op not in REDUCE_OPS:
+        raise ValueError(f"op must be one of {REDUCE_OPS}")
+    npt = np.dtype(GDF_TO_NP.get(int(col.c.dtype), np.int64))
+    out = torch.empty(16, dtype=torch.uint8, device="cuda")
+    getattr(libgdf, f"gdf_{op}_generic")(col.ptr, out.data_ptr(), 1)
+    return out[: npt.itemsize].cpu().numpy().view(npt)[0]
+
+
+def quantile(col: Column, q: float, method=None, sorted=False, sort_inplace=False):
+    """gdf_quantile_aprrox (method None: an element of the column, numpy scalar of its dtype) or gdf_quantile_exact (method
+    'linear' / 'lower' / 'higher' / 'midpoint' / 'nearest' or its gdf_quantile_method value: a float).  sorted: the column is
+    trusted to be sorted; sort_inplace: the column is left sorted; neither: it is not modified."""
+    ctx = new_context(flag_sorted=1 if sorted else 0, method=GDF_SORT, flag_sort_inplace=1 if sort_inplace else 0)
+    if method is None:
+        npt = np.dtype(GDF_TO_NP[int(col.c.dtype)])
+        res = np.zeros(1, dtype=npt)
+        libgdf.gdf_quantile_aprrox(col.ptr, float(q), res.ctypes.data, C.byref(ctx))
+        return res[0]
+    prec = QUANTILE_METHODS[method] if isinstance(method, str) else int(method)
+    res = C.c_double(0.0)
+    libgdf.gdf_quantile_exact(col.ptr, prec, float(q), C.addressof(res), C.byref(ctx))
+    return res.value
+
+
 def comparison(lhs: Column, rhs, op: int):
     """gpu_comparison (column rhs) or gpu_comparison_static_* (python scalar tagged with a numpy dtype)."""
     import torch

@@ -1190,6 +1190,34 @@ static gdf_error radixsort_api(const RadixPlan *plan, gdf_column *keycol, gdf_co
   return GDF_SUCCESS;
 }
 
+// quantile.hip (flag_sort_inplace): n elements of storage kind `kind` at `data` sorted ascending in place, in the order above
+// (NaN after +inf); the same images, LSD sort and gather as radixsort_api without a value column
+gdf_error sort_column_inplace(void *data, ElemKind kind, uint32_t n) {
+  if (n < 2) return GDF_SUCCESS;
+  const int kw = kind_width(kind);
+  DevBuf ka, kb, va, vb, vary, back;
+  RMM_TRY(ka.alloc(sizeof(uint64_t) * (size_t)n));
+  RMM_TRY(kb.alloc(sizeof(uint64_t) * (size_t)n));
+  RMM_TRY(va.alloc(sizeof(uint32_t) * (size_t)n));
+  RMM_TRY(vb.alloc(sizeof(uint32_t) * (size_t)n));
+  RMM_TRY(vary.alloc(sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(vary.p, 0, sizeof(unsigned long long), stream0()));
+  uint64_t *kin = ka.as<uint64_t>(), *kout = kb.as<uint64_t>();
+  uint32_t *vin = va.as<uint32_t>(), *vout = vb.as<uint32_t>();
+  const int grid = stream_grid(n, 1024);
+  GDF_LAUNCH("rsw_images", rsw_images, dim3(grid), dim3(256), 0, stream0(), (const void *)data, (int)kind, 0, (const uint32_t *)nullptr,
+             (const uint8_t *)nullptr, kin, vin, n, vary.as<unsigned long long>());
+  unsigned long long varying = 0;
+  HIP_TRY(read_back(&varying, vary.p, sizeof(varying)));
+  GDF_TRY((radix_sort_pairs<uint64_t, uint32_t>(kin, kout, vin, vout, n, varying)));
+  RMM_TRY(back.alloc((size_t)kw * n));
+  GDF_LAUNCH("rsw_gather", rsw_gather, dim3(grid), dim3(256), 0, stream0(), (const uint32_t *)vin, n, kw, (const void *)data, back.p);
+  HIP_TRY(hipMemcpyAsync(data, back.p, (size_t)kw * n, hipMemcpyDeviceToDevice, stream0()));
+  HIP_CHECK_LAST();
+  HIP_TRY(hipStreamSynchronize(stream0()));
+  return GDF_SUCCESS;
+}
+
 static gdf_error radixsort_generic(const RadixPlan *plan, gdf_column *keycol, gdf_column *valcol, int nseg, const unsigned *b, const unsigned *e) {
   GDF_REQUIRE(keycol && valcol, GDF_DATASET_EMPTY);
   GDF_REQUIRE(valcol->dtype == GDF_INT64, GDF_UNSUPPORTED_DTYPE);          // sorting.cu:224
