@@ -12,10 +12,9 @@
  * sizeof(gdf_context)==20; enums are positional ints.
  *
  * The header is plain C (usable from cgo / JNI / ctypes / cffi) and is also
- * what the C++ host code in libgdf_amd/csrc compiles against.  Entry points
- * that are outside the relational hot path are declared
- * through gdf_unsupported.def; they are exported and return
- * GDF_UNSUPPORTED_METHOD (or a null handle).
+ * what the C++ host code in libgdf_amd/csrc compiles against.  The 182
+ * element-wise operators are declared through gdf_elementwise.def.  read_csv
+ * and gdf_to_csr are exported and return GDF_UNSUPPORTED_METHOD.
  */
 #ifndef GDF_AMD_GDF_H
 #define GDF_AMD_GDF_H
@@ -328,21 +327,64 @@ gdf_error gdf_sum_squared_f32(gdf_column *col, float *dev_result, gdf_size_type 
 gdf_error gdf_quantile_exact(gdf_column *col_in, gdf_quantile_method prec, double q, void *t_erased_res, gdf_context *ctxt);
 gdf_error gdf_quantile_aprrox(gdf_column *col_in, double q, void *t_erased_res, gdf_context *ctxt);
 
-/* ======================================================================== *
- *  Out-of-scope entry points: exported, return GDF_UNSUPPORTED_METHOD.     *
- * ======================================================================== */
+/* --- element-wise operators (functions.h:380-675; reference src/binaryops.cu, unaryops.cu, datetimeops.cu):
+ *     csrc/elementwise.hip, prototypes in gdf_elementwise.def
+ *
+ * Every call is one kernel launch on the legacy default stream and returns after the output is written.  All argument
+ * checks run on the host before any device work; nothing (no data, no field of `output`) is written when an error is
+ * returned.  Data pointers need element alignment only (a column may be a slice); any size is accepted.
+ *   NULL       a NULL column pointer: GDF_UNSUPPORTED_METHOD, for all 182 entry points (the reference dereferences it).
+ *              A NULL data pointer of a non-empty column: GDF_INVALID_API_CALL.
+ *   binary     gdf_{add,sub,mul,floordiv}_{generic,i32,i64,f32,f64}, gdf_div_{generic,f32,f64},
+ *              gdf_{gt,ge,lt,le,eq,ne}_{generic,i8,i32,i64,f32,f64}, gdf_bitwise_{and,or,xor}_{generic,i8,i32,i64}.
+ *              Checks, in this order: either input of size 0: GDF_SUCCESS, nothing done.  lhs->size != rhs->size or
+ *              != output->size: GDF_COLUMN_SIZE_MISMATCH.  lhs->dtype != rhs->dtype: GDF_UNSUPPORTED_DTYPE.
+ *              output->dtype must be lhs->dtype for arithmetic and bit operations and GDF_INT8 for comparisons, else
+ *              GDF_UNSUPPORTED_DTYPE.  A typed entry point trusts its suffix for the element type.  _generic (after the
+ *              size-0 rule) dispatches on lhs->dtype: arithmetic INT32 / INT64 / FLOAT32 / FLOAT64; div FLOAT32 /
+ *              FLOAT64; comparisons INT8 / INT32 / INT64 / FLOAT32 / FLOAT64, DATE32 as int32, DATE64 and TIMESTAMP as
+ *              int64; bit operations INT8 / INT32 / INT64; anything else GDF_UNSUPPORTED_DTYPE.
+ *   values     integers wrap.  Float add / sub / mul / div are the correctly rounded IEEE operations.  Float floordiv
+ *              is floor(lhs / rhs) in the column type.  Integer floordiv is EXACT floor division (the reference divides
+ *              in double: the same for int32, off beyond 2^53 for int64); rhs == 0 gives 0 and INT_MIN / -1 gives
+ *              INT_MIN -- the reference leaves both unspecified -- and neither faults.  Comparisons write 0 / 1 as int8;
+ *              with a NaN operand only ne is 1.
+ *   nulls      (binary and math) a row is null when it is null in any input.  The output DATA at a null row is
+ *              unspecified (the reference leaves it unwritten, here it holds the operation applied to whatever the inputs
+ *              hold there); output->valid and output->null_count are not touched, as in the reference: the caller ANDs
+ *              the input masks.  The kernels do not read the masks.
+ *   math       gdf_{sin,cos,tan,asin,acos,atan,exp,log,sqrt,ceil,floor}_{generic,f32,f64}.  size 0: GDF_SUCCESS; sizes
+ *              differ: GDF_COLUMN_SIZE_MISMATCH; _generic takes FLOAT32 / FLOAT64, anything else GDF_UNSUPPORTED_DTYPE.
+ *              f32 uses the f32 routines of the device math library and f64 the f64 ones, built without fast-math; sqrt,
+ *              ceil and floor are exact, the others within a few ulp.
+ *   casts      gdf_cast_{generic,i8,i32,i64,f32,f64,date32,date64,timestamp}_to_{f32,f64,i8,i32,i64,date32,date64} and
+ *              .._to_timestamp(input, output, time_unit).  input->dtype must be the source the name says (generic: one of
+ *              the eight), else GDF_UNSUPPORTED_DTYPE; then the sizes must agree (GDF_COLUMN_SIZE_MISMATCH) unless
+ *              input->size is 0.  Then output->dtype is set -- and output->dtype_info.time_unit by _to_timestamp -- also
+ *              for size 0; when input->valid and output->valid are both non-NULL, ceil(size / 8) mask bytes are copied.
+ *              The conversion is the C conversion, except between date / time types: DATE32 (days) <-> DATE64 (ms),
+ *              DATE32 <-> TIMESTAMP(s|ms|us|ns), DATE64 <-> TIMESTAMP(s|us|ns) and TIMESTAMP <-> TIMESTAMP across units
+ *              multiply (wrapping) towards the finer unit and FLOOR-divide towards the coarser one.  DATE64 <->
+ *              TIMESTAMP(ms), equal units and TIME_UNIT_NONE on either side are plain copies.  Float -> integer of a NaN
+ *              or an out-of-range value is unspecified and does not fault.
+ *   datetime   gdf_extract_datetime_{year,month,day,hour,minute,second}.  Sizes differ: GDF_COLUMN_SIZE_MISMATCH;
+ *              output->dtype != GDF_INT16: GDF_UNSUPPORTED_DTYPE.  Input DATE32 (year / month / day only: hour, minute
+ *              and second answer GDF_UNSUPPORTED_DTYPE), DATE64 (ms) or TIMESTAMP in its time_unit (TIME_UNIT_NONE counts
+ *              as ms, as in the reference); anything else GDF_UNSUPPORTED_DTYPE.  The mask is copied as for the casts.
+ *              The fields are those of the proleptic Gregorian calendar with floor semantics on both sides of the epoch
+ *              (numpy.datetime64).  Two deliberate differences from the reference: at a negative exact multiple of a day
+ *              / hour / minute it yields hour 24 / minute 60 / second 60, this library 0; it narrows the day number to
+ *              32 bits, this library computes it in 64 and truncates the year to int16.
+ *   aliasing   output->data may be exactly lhs->data or rhs->data (input->data) when the element widths are equal;
+ *              partial overlap is undefined.
+ *   determinism  a second call on the same input gives bit-identical output.                                              */
 #define GDF_DECL_UNARY(name)        gdf_error name(gdf_column *input, gdf_column *output);
 #define GDF_DECL_UNARY_TU(name)     gdf_error name(gdf_column *input, gdf_column *output, gdf_time_unit time_unit);
 #define GDF_DECL_BINARY(name)       gdf_error name(gdf_column *lhs, gdf_column *rhs, gdf_column *output);
-#define GDF_DECL_RSORT(name)        gdf_error name(gdf_radixsort_plan_type *hdl, gdf_column *keycol, gdf_column *valcol);
-#define GDF_DECL_SEGSORT(name)      gdf_error name(gdf_segmented_radixsort_plan_type *hdl, gdf_column *keycol, gdf_column *valcol, \
-                                                   unsigned num_segments, unsigned *d_begin_offsets, unsigned *d_end_offsets);
-#include "gdf_unsupported.def"
+#include "gdf_elementwise.def"
 #undef GDF_DECL_UNARY
 #undef GDF_DECL_UNARY_TU
 #undef GDF_DECL_BINARY
-#undef GDF_DECL_RSORT
-#undef GDF_DECL_SEGSORT
 
 /* one-off shapes (functions.h:108-224,692-705,774-785; io_functions.h) */
 gdf_ipc_parser_type *gdf_ipc_parser_open(const uint8_t *schema, size_t length);
@@ -377,6 +419,7 @@ gdf_error   gdf_segmented_radixsort_plan_free(gdf_segmented_radixsort_plan_type 
 gdf_error   gpu_concat(gdf_column *lhs, gdf_column *rhs, gdf_column *output);
 gdf_error   gpu_hash_columns(gdf_column **columns_to_hash, int num_columns, gdf_column *output_column, void *stream);
 gdf_error   gdf_order_by(size_t nrows, gdf_column *cols, size_t ncols, void **d_cols, int *d_types, size_t *d_indx);
+/* out of scope: exported, return GDF_UNSUPPORTED_METHOD (csrc/unsupported.cpp) */
 gdf_error   read_csv(csv_read_arg *args);
 gdf_error   gdf_to_csr(gdf_column **gdfData, int num_cols, csr_gdf *csrReturn);
 

@@ -156,6 +156,26 @@ for _op in ("sum", "product", "min", "max", "sum_squared"):
     for _sfx in (("generic", "f64", "f32") if _op == "sum_squared" else ("generic", "f64", "f32", "i64", "i32", "i8")):
         _PROTOTYPES[f"gdf_{_op}_{_sfx}"] = (None, [_COLP, C.c_void_p, C.c_size_t])
 
+# element-wise operators (csrc/elementwise.hip, include/gdf/gdf_elementwise.def): three signature shapes
+BINARY_OPS = {**{_op: ("generic", "i32", "i64", "f32", "f64") for _op in ("add", "sub", "mul", "floordiv")},
+              "div": ("generic", "f32", "f64"),
+              **{_op: ("generic", "i8", "i32", "i64", "f32", "f64") for _op in ("gt", "ge", "lt", "le", "eq", "ne")},
+              **{_op: ("generic", "i8", "i32", "i64") for _op in ("bitwise_and", "bitwise_or", "bitwise_xor")}}
+MATH_OPS = ("sin", "cos", "tan", "asin", "acos", "atan", "exp", "log", "sqrt", "ceil", "floor")
+CAST_SOURCES = ("generic", "i8", "i32", "i64", "f32", "f64", "date32", "date64", "timestamp")
+CAST_TARGETS = ("f32", "f64", "i8", "i32", "i64", "date32", "date64", "timestamp")
+DATETIME_FIELDS = ("year", "month", "day", "hour", "minute", "second")
+ELEMENTWISE_NAMES = {
+    "binary": [f"gdf_{_op}_{_sfx}" for _op, _sfxs in BINARY_OPS.items() for _sfx in _sfxs],
+    "unary": ([f"gdf_{_op}_{_sfx}" for _op in MATH_OPS for _sfx in ("generic", "f32", "f64")]
+              + [f"gdf_cast_{_src}_to_{_dst}" for _dst in CAST_TARGETS[:-1] for _src in CAST_SOURCES]
+              + [f"gdf_extract_datetime_{_f}" for _f in DATETIME_FIELDS]),
+    "unary_time_unit": [f"gdf_cast_{_src}_to_timestamp" for _src in CAST_SOURCES],
+}
+for _shape, _args in (("binary", [_COLP, _COLP, _COLP]), ("unary", [_COLP, _COLP]), ("unary_time_unit", [_COLP, _COLP, C.c_int])):
+    for _name in ELEMENTWISE_NAMES[_shape]:
+        _PROTOTYPES[_name] = (None, _args)
+
 _RMM_PROTOTYPES = {
     "rmmInitialize": (None, [C.POINTER(rmmOptions_t)]),
     "rmmFinalize": (None, []),

@@ -11,8 +11,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._binding import GDF_UNSUPPORTED_METHOD, GDFError, gdf_column, libgdf
-from .columns import (GDF_HASH, GDF_HASH_MURMUR3, GDF_SORT, GDF_TO_NP, Column, column_array, new_context)
+from ._binding import (BINARY_OPS, CAST_TARGETS, DATETIME_FIELDS, GDF_UNSUPPORTED_METHOD, MATH_OPS, GDFError, gdf_column,
+                       libgdf)
+from .columns import (GDF_DTYPES, GDF_HASH, GDF_HASH_MURMUR3, GDF_SORT, GDF_TO_NP, TIME_UNITS, Column, column_array,
+                      new_context)
 
 _hip = None
 
@@ -369,6 +371,81 @@ def quantile(col: Column, q: float, method=None, sorted=False, sort_inplace=Fals
     res = C.c_double(0.0)
     libgdf.gdf_quantile_exact(col.ptr, prec, float(q), C.addressof(res), C.byref(ctx))
     return res.value
+
+
+# ---- element-wise operators (csrc/elementwise.hip) ---------------------------------------------------------------------------
+_CAST_TARGET_DTYPE = dict(f32="GDF_FLOAT32", f64="GDF_FLOAT64", i8="GDF_INT8", i32="GDF_INT32", i64="GDF_INT64",
+                          date32="GDF_DATE32", date64="GDF_DATE64", timestamp="GDF_TIMESTAMP")
+
+
+def _empty_mask(n: int):
+    import torch
+    return torch.zeros(((n + 7) // 8 + 63) // 64 * 64 or 64, dtype=torch.uint8, device="cuda")
+
+
+def _new_output(n: int, gdf_dtype: int, valid=None, null_count: int = 0, time_unit=None) -> Column:
+    import torch
+    data = torch.empty(max(n, 1), dtype=getattr(torch, np.dtype(GDF_TO_NP[gdf_dtype]).name), device="cuda")
+    return Column(data, valid, gdf_dtype, size=n, null_count=null_count, time_unit=time_unit)
+
+
+def binary_op(name: str, lhs: Column, rhs: Column) -> Column:
+    """gdf_<name>_generic: add / sub / mul / floordiv / div, gt / ge / lt / le / eq / ne (int8 0 / 1) or bitwise_and / _or /
+    _xor of two columns of one dtype.  The library writes the data only; the output mask is the AND of the input masks,
+    computed here, and the data at a null row is unspecified."""
+    if name not in BINARY_OPS:
+        raise ValueError(f"name must be one of {tuple(BINARY_OPS)}")
+    n = lhs.size
+    masks = [c.valid for c in (lhs, rhs) if c.valid is not None]
+    valid, nulls = None, 0
+    if masks:
+        nb = (n + 7) // 8
+        valid = _empty_mask(n)
+        valid[:nb] = masks[0][:nb] if len(masks) == 1 else masks[0][:nb] & masks[1][:nb]
+        if n % 8:
+            valid[nb - 1] &= (1 << (n % 8)) - 1
+        ones = int(sum(int((valid[:nb] >> b & 1).sum()) for b in range(8)))
+        nulls = n - ones
+    out_dtype = GDF_DTYPES["GDF_INT8"] if len(BINARY_OPS[name]) == 6 else int(lhs.c.dtype)
+    out = _new_output(n, out_dtype, valid, nulls)
+    getattr(libgdf, f"gdf_{name}_generic")(lhs.ptr, rhs.ptr, out.ptr)
+    return out
+
+
+def unary_op(name: str, col: Column) -> Column:
+    """gdf_<name>_generic: sin / cos / tan / asin / acos / atan / exp / log / sqrt / ceil / floor of a FLOAT32 or FLOAT64
+    column.  The output carries a copy of the input's mask; the data at a null row is unspecified."""
+    if name not in MATH_OPS:
+        raise ValueError(f"name must be one of {MATH_OPS}")
+    out = _new_output(col.size, int(col.c.dtype), col.valid.clone() if col.valid is not None else None, int(col.c.null_count))
+    getattr(libgdf, f"gdf_{name}_generic")(col.ptr, out.ptr)
+    return out
+
+
+def cast(col: Column, to: str, time_unit=None) -> Column:
+    """gdf_cast_generic_to_<to>, to one of f32 / f64 / i8 / i32 / i64 / date32 / date64 / timestamp; time_unit ('s' / 'ms' /
+    'us' / 'ns' or a gdf_time_unit value) is the unit of a timestamp result.  The library copies the mask."""
+    if to not in CAST_TARGETS:
+        raise ValueError(f"to must be one of {CAST_TARGETS}")
+    n = col.size
+    out = _new_output(n, GDF_DTYPES[_CAST_TARGET_DTYPE[to]], _empty_mask(n) if col.valid is not None else None, int(col.c.null_count))
+    if to == "timestamp":
+        unit = 0 if time_unit is None else (TIME_UNITS[time_unit] if isinstance(time_unit, str) else int(time_unit))
+        libgdf.gdf_cast_generic_to_timestamp(col.ptr, out.ptr, unit)
+    else:
+        getattr(libgdf, f"gdf_cast_generic_to_{to}")(col.ptr, out.ptr)
+    return out
+
+
+def extract_datetime(field: str, col: Column) -> Column:
+    """gdf_extract_datetime_<field> (year / month / day / hour / minute / second) of a DATE32, DATE64 or TIMESTAMP column:
+    an INT16 column with a copy of the input's mask."""
+    if field not in DATETIME_FIELDS:
+        raise ValueError(f"field must be one of {DATETIME_FIELDS}")
+    n = col.size
+    out = _new_output(n, GDF_DTYPES["GDF_INT16"], _empty_mask(n) if col.valid is not None else None, int(col.c.null_count))
+    getattr(libgdf, f"gdf_extract_datetime_{field}")(col.ptr, out.ptr)
+    return out
 
 
 def comparison(lhs: Column, rhs, op: int):

@@ -15,6 +15,7 @@ from ._binding import gdf_column, gdf_context, libgdf
 # gdf_dtype values (include/gdf/gdf.h)
 GDF_DTYPES = dict(GDF_invalid=0, GDF_INT8=1, GDF_INT16=2, GDF_INT32=3, GDF_INT64=4, GDF_FLOAT32=5, GDF_FLOAT64=6,
                   GDF_DATE32=7, GDF_DATE64=8, GDF_TIMESTAMP=9, GDF_CATEGORY=10, GDF_STRING=11, N_GDF_TYPES=12)
+TIME_UNITS = dict(none=0, s=1, ms=2, us=3, ns=4)          # gdf_time_unit
 GDF_SORT, GDF_HASH = 0, 1
 GDF_HASH_MURMUR3, GDF_HASH_IDENTITY = 0, 1
 GDF_EQUALS, GDF_NOT_EQUALS, GDF_LESS_THAN, GDF_LESS_THAN_OR_EQUALS, GDF_GREATER_THAN, GDF_GREATER_THAN_OR_EQUALS = range(6)
@@ -71,7 +72,10 @@ def _torch_np_dtype(t):
 class Column:
     """A ``gdf_column`` plus the torch tensors that own its device memory."""
 
-    def __init__(self, data=None, valid=None, dtype: int | None = None, size: int | None = None, null_count: int = 0):
+    def __init__(self, data=None, valid=None, dtype: int | None = None, size: int | None = None, null_count: int = 0,
+                 time_unit: int | str | None = None):
+        """time_unit (a gdf_time_unit value or 's' / 'ms' / 'us' / 'ns'): dtype_info.time_unit of a GDF_TIMESTAMP column;
+        None leaves it TIME_UNIT_NONE."""
         self.data = data
         self.valid = valid
         self.c = gdf_column()
@@ -81,6 +85,8 @@ class Column:
             n = data.numel() if size is None else size
             libgdf.gdf_column_view_augmented(C.byref(self.c), data.data_ptr() if data.numel() else None,
                                              valid.data_ptr() if valid is not None else None, n, dtype, null_count)
+        if time_unit is not None:
+            self.c.dtype_info.time_unit = TIME_UNITS[time_unit] if isinstance(time_unit, str) else int(time_unit)
 
     @property
     def ptr(self):
@@ -105,7 +111,8 @@ def column_from_tensor(data, valid=None, dtype: int | None = None, null_count: i
     return Column(data, valid, dtype, null_count=null_count)
 
 
-def column_from_numpy(arr: np.ndarray, valid: np.ndarray | None = None, dtype: int | None = None, device="cuda") -> Column:
+def column_from_numpy(arr: np.ndarray, valid: np.ndarray | None = None, dtype: int | None = None, device="cuda",
+                      time_unit: int | str | None = None) -> Column:
     """Upload a host array (and optional bool validity vector) -- test convenience."""
     import torch
     arr = np.ascontiguousarray(arr)
@@ -115,7 +122,7 @@ def column_from_numpy(arr: np.ndarray, valid: np.ndarray | None = None, dtype: i
     if valid is not None:
         v = torch.from_numpy(mask_from_bools(valid)).to(device)
         nulls = int(len(valid) - np.count_nonzero(valid))
-    return Column(t, v, dtype if dtype is not None else get_dtype(arr.dtype), null_count=nulls)
+    return Column(t, v, dtype if dtype is not None else get_dtype(arr.dtype), null_count=nulls, time_unit=time_unit)
 
 
 def column_array(cols):
