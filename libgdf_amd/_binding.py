@@ -196,12 +196,11 @@ GDF_COLUMN_SIZE_TOO_BIG = 4
 GDF_INT64 = 4                        # include/gdf/gdf.h gdf_dtype
 
 
-# LIBGDF_AMD_LAB=1: bind the LAB build of libgdf.so (lib/lab/, csrc/lab.h: experiment knobs compiled in and read from the
-# environment) instead of the shipped one.  Only the tuning scripts under tools/gpu/ set it; the choice is made HERE, in the
-# Python binding -- the shipped libgdf.so itself reads no environment variable.
-# (LIBGDF_AMD_LAB=<subdirectory of lib/>: any other side-by-side build, e.g. the previous commit's kernels for an A/B on one box.)
+# LIBGDF_AMD_LAB=<subdirectory of lib/>: bind a side-by-side build of libgdf.so (lib/<subdirectory>/libgdf.so) instead of the shipped
+# one, e.g. the previous commit's kernels for an A/B on one box.  The choice is made HERE, in the Python binding -- libgdf.so itself
+# reads no environment variable.
 LAB_BUILD = os.environ.get("LIBGDF_AMD_LAB", "")
-LAB_BUILD = "" if LAB_BUILD == "0" else ("lab" if LAB_BUILD == "1" else LAB_BUILD)
+LAB_BUILD = "" if LAB_BUILD == "0" else LAB_BUILD
 
 
 def _load(name):

@@ -109,7 +109,7 @@ static void launch_compare(const void *l, const void *r, R scalar, void *out, in
   if constexpr (RIGHT_SCALAR || sizeof(L) == sizeof(R)) {
     const bool aligned = ((uintptr_t)l % 16 == 0) && (RIGHT_SCALAR || (uintptr_t)r % 16 == 0) && ((uintptr_t)out % 16 == 0);
     const int64_t nvec = n / EPV;
-    if (aligned && nvec >= 1024 && !lab::knob_on("GDF_FL_NO_VEC")) {
+    if (aligned && nvec >= 1024) {
       GDF_LAUNCH("compare", (compare_vec_kernel<L, R, RIGHT_SCALAR>), dim3(stream_grid((size_t)nvec, FL_THREADS * 4)), dim3(FL_THREADS), 0,
                  stream0(), (const L *)l, (const R *)r, scalar, (int8_t *)out, nvec, op);
       done = nvec * EPV;
@@ -739,8 +739,7 @@ static gdf_error compact(Pred pred, int64_t n, int width, const void *in, void *
       auto rounds = [&](auto kernel) -> gdf_error {
         int fit = 1;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, (const void *)kernel, FL_THREADS, 0));
-        const int want = (int)lab::knob_int("GDF_FL_WGS_PER_CU", 4);
-        size_t grid = (size_t)device_cu_count() * (size_t)std::max(1, std::min(std::min(want, fit), 4));
+        size_t grid = (size_t)device_cu_count() * (size_t)std::max(1, std::min(fit, 4));
         if (grid > (size_t)4 * FL_THREADS) grid = (size_t)4 * FL_THREADS;       // (the slots one poll covers)
         if (grid > ntiles) grid = (size_t)ntiles;        // (a grid beyond the super-tiles: the spare workgroups leave at once)
         DevBuf st;
@@ -762,15 +761,12 @@ static gdf_error compact(Pred pred, int64_t n, int width, const void *in, void *
         return GDF_SUCCESS;
       };
       gdf_error e;
-      const int K = (int)lab::knob_int("GDF_FL_ROUNDS_K", 4);      // tiles per workgroup and round (stencil_rounds_kernel)
-#define FL_ROUNDS_W(W) (K == 1 ? rounds(stencil_rounds_kernel<W, 1>) : K == 2 ? rounds(stencil_rounds_kernel<W, 2>) : rounds(stencil_rounds_kernel<W, 4>))
-      switch (width) {
-        case 1: e = FL_ROUNDS_W(1); break;
-        case 2: e = FL_ROUNDS_W(2); break;
-        case 4: e = FL_ROUNDS_W(4); break;
-        default: e = FL_ROUNDS_W(8); break;
+      switch (width) {                                   // four tiles per workgroup and round (stencil_rounds_kernel)
+        case 1: e = rounds(stencil_rounds_kernel<1, 4>); break;
+        case 2: e = rounds(stencil_rounds_kernel<2, 4>); break;
+        case 4: e = rounds(stencil_rounds_kernel<4, 4>); break;
+        default: e = rounds(stencil_rounds_kernel<8, 4>); break;
       }
-#undef FL_ROUNDS_W
       if (e != GDF_UNSUPPORTED_METHOD) return e;
       *kept = 0;
     }
@@ -796,8 +792,7 @@ static gdf_error compact(Pred pred, int64_t n, int width, const void *in, void *
     // thread-consecutive rows win while few rows survive (10 % kept: 0.19 vs 0.33 ms per 1e8 rows); at 50 % the
     // ballot kernel below is ahead again (0.39 vs 0.42 ms), so the number of keepers -- known after the scan -- decides
     HIP_TRY(read_back(kept, counts.as<uint64_t>() + nchunks, sizeof(uint64_t)));
-    if (((uintptr_t)pred.stencil & 15) == 0 && ((uintptr_t)in & 15) == 0 && chunk % FLS_ROWS == 0 && width != 0 && !lab::knob_on("GDF_FL_NO_VEC") &&
-        !lab::knob_on("GDF_FL_NO_STAGE")) {
+    if (((uintptr_t)pred.stencil & 15) == 0 && ((uintptr_t)in & 15) == 0 && chunk % FLS_ROWS == 0 && width != 0) {
       switch (width) {
         case 1: GDF_LAUNCH("compact_write", stencil_stage_write_kernel<1>, g, b, 0, stream0(), pred.stencil, pred.valid, n, chunk, counts.as<uint64_t>(), in, out); break;
         case 2: GDF_LAUNCH("compact_write", stencil_stage_write_kernel<2>, g, b, 0, stream0(), pred.stencil, pred.valid, n, chunk, counts.as<uint64_t>(), in, out); break;
@@ -808,7 +803,7 @@ static gdf_error compact(Pred pred, int64_t n, int width, const void *in, void *
       HIP_TRY(hipStreamSynchronize(stream0()));        // (the keeper count was read above; the counts go out of scope)
       return GDF_SUCCESS;
     }
-    if (((uintptr_t)pred.stencil & 15) == 0 && chunk % 16 == 0 && width != 0 && *kept * 3 < (uint64_t)n && !lab::knob_on("GDF_FL_NO_VEC")) {
+    if (((uintptr_t)pred.stencil & 15) == 0 && chunk % 16 == 0 && width != 0 && *kept * 3 < (uint64_t)n) {
       switch (width) {
         case 1: GDF_LAUNCH("compact_write", stencil_write_kernel<1>, g, b, 0, stream0(), pred.stencil, pred.valid, n, chunk, counts.as<uint64_t>(), in, out); break;
         case 2: GDF_LAUNCH("compact_write", stencil_write_kernel<2>, g, b, 0, stream0(), pred.stencil, pred.valid, n, chunk, counts.as<uint64_t>(), in, out); break;

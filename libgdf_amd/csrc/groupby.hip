@@ -1838,7 +1838,6 @@ struct GbHot {
   uint32_t window;                 // key >> GBP_HOT_BITS of the hot ids (the key WITHOUT its validity bit)
   unsigned long long *gacc;        // the global cells the partials are merged into (indexed by key)
   unsigned int *grows, *gvalid;
-  int dbg;                         // LAB build: ablation bits (knob GDF_GBP_HOT_DBG), 0 in production
   int plain_rank;                  // the sample found no partition with a large share of the rows that are ranked: gbp_rank_plain
 };
 
@@ -2191,21 +2190,6 @@ __global__ __launch_bounds__(GBP_SC_THREADS) void gbp_scatter_static(KeyTable t,
   };
   auto request = [&](int64_t tile, int64_t end) {
     const uint32_t tid = gbp_opaque_tid();
-#ifdef GDF_AMD_LAB
-    if (HOT && (LAB_BITS(hot.dbg) & 16)) {            // LAB bit 16: read-once input as non-temporal loads (do the streams push the write fronts out of L2?)
-#pragma unroll
-      for (int k = 0; k < GBP_ITEMS; ++k) if (VMASK) vb[k] = __builtin_nontemporal_load(val.valid + (row_of(tile, end, k, tid) >> 3));
-#pragma unroll
-      for (int k = 0; k < GBP_ITEMS; ++k) img[k] = __builtin_nontemporal_load((const uint64_t *)val.data + row_of(tile, end, k, tid));
-#pragma unroll
-      for (int k = 0; k < GBP_ITEMS; ++k) r0[k] = __builtin_nontemporal_load((const W0 *)t.col[0].data + row_of(tile, end, k, tid));
-      if (K1 >= 0) {
-#pragma unroll
-        for (int k = 0; k < GBP_ITEMS; ++k) r1[k] = __builtin_nontemporal_load((const W1 *)t.col[1].data + row_of(tile, end, k, tid));
-      }
-      return;
-    }
-#endif
 #pragma unroll
     for (int k = 0; k < GBP_ITEMS; ++k) if (VMASK) vb[k] = val.valid[row_of(tile, end, k, tid) >> 3];
 #pragma unroll
@@ -2243,7 +2227,7 @@ __global__ __launch_bounds__(GBP_SC_THREADS) void gbp_scatter_static(KeyTable t,
   // chunk -> workgroup: XCD x (workgroups x, x + 8, ...: MI355X_MICROARCH.md "Workgroup dispatch") takes the x-th EIGHTH of the chunks, its
   // workgroups round-robin inside it.  The regions of chunks c and c + 1 are neighbours inside every partition and share their
   // boundary line; with c -> workgroup c % grid they sat behind two different, non-coherent L2s (the trick of jk_scatter2's tiles)
-  const bool xcd_map = (gridDim.x & 7u) == 0 && !(LAB_BITS(hot.dbg) & 32);
+  const bool xcd_map = (gridDim.x & 7u) == 0;
   const int per_xcd = (nchunks + 7) / 8, first = xcd_map ? (int)(blockIdx.x >> 3) : (int)blockIdx.x, step = xcd_map ? (int)(gridDim.x >> 3) : (int)gridDim.x;
   for (int ci = first; xcd_map ? ci < per_xcd : ci < nchunks; ci += step) {
     const int c = xcd_map ? (int)(blockIdx.x & 7u) * per_xcd + ci : ci;
@@ -2318,7 +2302,7 @@ __global__ __launch_bounds__(GBP_SC_THREADS) void gbp_scatter_static(KeyTable t,
         hotmask &= livemask;
 #pragma unroll
         for (int k = 0; k < GBP_ITEMS; ++k) {
-          if (((hotmask >> k) & 1u) && !(LAB_BITS(hot.dbg) & 1)) {          // (LAB bit 1: hot rows vanish without their atomics)
+          if ((hotmask >> k) & 1u) {
             const uint32_t id = (k32[k] >> vbit) & (GBP_HOT_IDS - 1u);
             atomicAdd(&hrows[id], 1u);
             if (!VBIT || (k32[k] & 1u)) {
@@ -2328,7 +2312,6 @@ __global__ __launch_bounds__(GBP_SC_THREADS) void gbp_scatter_static(KeyTable t,
           }
         }
         livemask &= ~hotmask;
-        if (LAB_BITS(hot.dbg) & 4) livemask = 0;            // (LAB bit 4: no cold row travels)
       }
       if (hot.plain_rank) gbp_rank_plain<GBP_ITEMS>(hist, part, livemask, rk);      // (uniform)
       else gbp_rank<GBP_ITEMS>(hist, part, livemask, rk);
@@ -2401,10 +2384,6 @@ __global__ __launch_bounds__(GBP_SC_THREADS) void gbp_scatter_static(KeyTable t,
           }
         }
       };
-#ifdef GDF_AMD_LAB
-      const uint32_t lab_span = (uint32_t)(t.nrows / gridDim.x) - (uint32_t)GBP_SC_TILE;
-      const uint32_t lab_stream = blockIdx.x * (uint32_t)(t.nrows / gridDim.x) + (uint32_t)(((tile - begin) / GBP_SC_TILE) * CAP) % (lab_span ? lab_span : 1u);
-#endif
       auto flush = [&](uint32_t round0) {
         // every LDS read first (the record, then its partition's base), then the stores; slots beyond the round re-read slot 0
         uint32_t kk[FLUSH_ITEMS], gb[FLUSH_ITEMS];
@@ -2423,12 +2402,8 @@ __global__ __launch_bounds__(GBP_SC_THREADS) void gbp_scatter_static(KeyTable t,
 #pragma unroll
         for (int k = 0; k < FLUSH_ITEMS; ++k) {
           const uint32_t j = ftid + k * GBP_SC_THREADS;
-          uint32_t dst = gb[k] + round0 + j;
-#ifdef GDF_AMD_LAB
-          // LAB bit 8: the same records as one contiguous stream per workgroup (what would the stores cost without the short runs?)
-          if (LAB_BITS(hot.dbg) & 8) { dst = lab_stream + j; }
-#endif
-          if (j < cnt && (!SPEC || (int32_t)dst >= 0) && !(LAB_BITS(hot.dbg) & 2)) rec_out[dst] = GbRec{(uint32_t)vv[k], (uint32_t)(vv[k] >> 32), kk[k]};   // (LAB bit 2: no stores)
+          const uint32_t dst = gb[k] + round0 + j;
+          if (j < cnt && (!SPEC || (int32_t)dst >= 0)) rec_out[dst] = GbRec{(uint32_t)vv[k], (uint32_t)(vv[k] >> 32), kk[k]};
         }
       };
       // HOT: the stage holds CAP < TILE records; a tile with more cold rows than that (the sample mispredicted the window) sends its
@@ -2581,7 +2556,7 @@ static gdf_error gb_path_direct(GbJob &j, bool *done) {
     // The exact ranges cost a pass over the keys (0.25 of C2's 0.66 ms).  With ONE key column the window is first
     // guessed from a 65536-row prefix and widened to the whole id space; a row outside it raises a flag and the
     // attempt is repeated with the exact range.
-    const bool guess_first = ncols == 1 && n > (1 << 20) && !lab::knob_on("GDF_GB_NO_GUESS");
+    const bool guess_first = ncols == 1 && n > (1 << 20);
     for (int attempt = guess_first ? 0 : 1; attempt < 2; ++attempt) {
       std::vector<long long> h(2 * ncols);
       KeyTable tr = t;
@@ -2695,11 +2670,9 @@ static gdf_error gb_path_dense(GbJob &j, bool *done) {
   // 2^18 entries of 16 bytes: at most 6 % load with the 16384 groups this path takes.  Smaller tables were tried for L2
   // locality and LOST -- C2's sparse twin, dict build + aggregate: 2^15 0.82 + 0.92 ms, 2^16 0.70 + 0.84, 2^17 0.64 + 0.80,
   // 2^18 0.61 + 0.77 -- a key that is not in its home slot costs a dependent walk, which matters more than the footprint.
-  // GDF_GB_DICT_BITS: experiment switch.
-  const int dict_bits = (int)lab::knob_int("GDF_GB_DICT_BITS", 18);
-  const uint64_t tmax = 1ull << (dict_bits >= 15 && dict_bits <= 20 ? dict_bits : 18);
+  const uint64_t tmax = 1ull << 18;
   uint64_t T = cap_max < tmax ? cap_max : tmax;
-  if (plan.packed && !lab::knob_on("GDF_GB_NO_DENSE")) {
+  if (plan.packed) {
     DevBuf dict, flags, group_slot;
     RMM_TRY(dict.alloc(sizeof(GbDictEntry) * (T + 1)));
     RMM_TRY(flags.alloc(sizeof(unsigned int) * 8));           // [0..2] the dictionary's, [4..7] the LDS dictionary's state (gb_ld_image)
@@ -2879,7 +2852,7 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
   // FUSED: one partition pass straight from the raw columns (gbp_count / gbp_scatter) instead of pair build + radix sort
   bool fused = false;
   if constexpr (sizeof(K) == 4)
-    fused = part_bits >= 1 && part_bits <= GBP_MAX_PART_BITS && n >= ((int64_t)1 << 20) && !lab::knob_on("GDF_GB_NO_FUSED");
+    fused = part_bits >= 1 && part_bits <= GBP_MAX_PART_BITS && n >= ((int64_t)1 << 20);
   if (guessed && !fused) { *done = false; return GDF_SUCCESS; }      // only the fused kernels check keys against a guessed plan
   DevBuf ka, kb, pa, pb, fl;
   if (fused) {
@@ -2914,9 +2887,7 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
     if constexpr (sizeof(K) == 4) {
       const uint32_t P = 1u << part_bits;
       const int low = vbit + id_bits;
-      int max_chunks = GBP_MAX_CHUNKS;
-      if (lab::knob_int("GDF_GBP_CHUNKS", 0) > 0) max_chunks = (int)lab::knob_int("GDF_GBP_CHUNKS", 0);      // experiment switch
-      int64_t chunk = (n + max_chunks - 1) / max_chunks;
+      int64_t chunk = (n + GBP_MAX_CHUNKS - 1) / GBP_MAX_CHUNKS;
       chunk = (chunk + GBP_TILE - 1) / GBP_TILE * GBP_TILE;
       const int nchunks = (int)((n + chunk - 1) / chunk);
       DevBuf hist, d_start, d_flags;
@@ -2933,25 +2904,21 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
       // partition (C5: int32 values 0..15 under 2^13 ids) and that has no nulls cannot change a row's partition or drop the row:
       // the count does not read it (8 instead of 12 B per row on C5) and the scatter kernel, which reads every column anyway,
       // checks its values against a guessed range.  Only with the statically typed scatter kernels (they carry that check).
-      const bool val_sig = (val.kind == K_I64 || val.kind == K_F64) && fold_op != OP_COUNT && (!vbit || val.valid) && !lab::knob_on("GDF_GBP_OLD");
-      const bool skip_low = key_sig && val_sig && t.ncols == 2 && !t.col[1].valid && sp.shift[1] + sp.bits[1] + vbit <= low &&
-                            !lab::knob_on("GDF_GBP_COUNT_ALL");
+      const bool val_sig = (val.kind == K_I64 || val.kind == K_F64) && fold_op != OP_COUNT && (!vbit || val.valid);
+      const bool skip_low = key_sig && val_sig && t.ncols == 2 && !t.col[1].valid && sp.shift[1] + sp.bits[1] + vbit <= low;
       const int ck1 = skip_low ? -2 : k1;
       // record layout: partition-major -- hist[p][chunk], one scan gives every (partition, chunk) its place inside the partition's
-      // contiguous range.  (LAB knob GDF_GBP_CHUNK_MAJOR: [chunk][partition] segments, every workgroup's 2048 write fronts inside
-      // its own ~12 MB window -- the layout experiment of profiles/r3_*_c5_layout.md; the aggregation does not read that layout,
-      // the knob only times the scatter.)
-      const bool chunk_major = lab::knob_on("GDF_GBP_CHUNK_MAJOR");
-      const uint32_t qstride = chunk_major ? 1u : (uint32_t)nchunks, cstride = chunk_major ? P : 1u;
+      // contiguous range
+      const uint32_t qstride = (uint32_t)nchunks, cstride = 1u;
       // HOT WINDOW (GbHot): the densest aligned window of GBP_HOT_IDS ids in a strided sample, when it holds enough of the rows to
       // pay for 64 KB of LDS in the scatter kernel.  Statically typed scatter kernels only; a key column the count does not read
       // (skip_low) must lie below the window bits, so that the count can tell hot rows from their first column alone.
       uint32_t hot_window = GBP_NO_HOT;
-      const bool lean_sig = key_sig && val_sig && !lab::knob_on("GDF_GBP_OLD");
+      const bool sig = key_sig && val_sig;         // the statically typed scatter kernels (gbp_scatter_static)
       const dim3 sgrid(nchunks < NUM_CU ? nchunks : NUM_CU);
-      const bool hot_ok = lean_sig && id_bits == GB_PART_ID_BITS && !chunk_major && n >= ((int64_t)1 << 22) && !lab::path_on("GDF_GBP_NO_HOT");
+      const bool hot_ok = sig && id_bits == GB_PART_ID_BITS && n >= ((int64_t)1 << 22) && !lab::path_on("GDF_GBP_NO_HOT");
       // SPECULATIVE layout (GbSpec): no count pass; GDF_GBP_SPEC_MIN_ROWS / GDF_GBP_NO_SPEC: test switches
-      const bool spec_wanted = allow_spec && lean_sig && id_bits == GB_PART_ID_BITS && !chunk_major && !lab::path_on("GDF_GBP_NO_SPEC") &&
+      const bool spec_wanted = allow_spec && sig && id_bits == GB_PART_ID_BITS && !lab::path_on("GDF_GBP_NO_SPEC") &&
                                n >= lab::path_int("GDF_GBP_SPEC_MIN_ROWS", (long long)1 << 24);
       GbSpec spec{};
       int plain_rank = 0;                 // GbHot::plain_rank, decided from the sample below
@@ -3089,8 +3056,7 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
       if (!is_spec && skip_low && sp.shift[1] + sp.bits[1] > GBP_HOT_BITS) hot_window = GBP_NO_HOT;
       // the cells the partial aggregates are merged into: made BEFORE the scatter kernel, which merges the hot window's (make_cells above)
       if (hot_window != GBP_NO_HOT && !cells_ready) GDF_TRY(make_cells());
-      const GbHot hot{hot_window, gacc.as<unsigned long long>(), grows.as<unsigned int>(), gvalid.as<unsigned int>(),
-                      (int)lab::knob_int("GDF_GBP_HOT_DBG", 0), plain_rank};
+      const GbHot hot{hot_window, gacc.as<unsigned long long>(), grows.as<unsigned int>(), gvalid.as<unsigned int>(), plain_rank};
       auto count = [&](auto kernel) {
         GDF_LAUNCH("gbp_count", kernel, dim3(nchunks < NUM_CU * 2 ? nchunks : NUM_CU * 2), dim3(GBP_THREADS), 0, stream0(), t, sp, low, vbit, P,
                    chunk, nchunks, hist.as<uint32_t>(), d_flags.as<unsigned int>(), qstride, cstride, hot_window);
@@ -3106,8 +3072,6 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
       if (!is_spec) GDF_TRY(scan_u32(hist.as<uint32_t>(), hist.as<uint32_t>(), (size_t)P * nchunks + 1, false));
       const bool is_hot = hot_window != GBP_NO_HOT;
       const size_t slds = gbp_scatter_lds(is_hot);
-      const bool lean = !lab::knob_on("GDF_GBP_OLD");              // A/B switch: the scatter kernel with the type switches for every shape
-      const bool sig = lean && key_sig && val_sig;
       int launch_chunks = nchunks;       // (a calibration run of the placement tournament takes the first quarter of the chunks)
       auto run_scatter = [&]() -> gdf_error {
       if (sig) {
@@ -3147,7 +3111,7 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
       // PLACEMENT TOURNAMENT of the speculative record buffer (as for the join's tuple buffers, join.hip): while the pool is comparing
       // placements for this size, every candidate is timed on the real kernel over the first quarter of the chunks; the fill counters,
       // the flags and the hot window's cells are set back behind each run
-      if (is_spec && sig && !lab::knob_on("GDF_GBP_NO_CALIBRATE")) {
+      if (is_spec && sig) {
         const size_t rec_bytes = sizeof(GbRec) * (size_t)(hp[P]);
         for (int round = 0; round <= GB_PLACE_DRAWS && ka.measure; ++round) {
           PlaceRound charge;
@@ -3164,11 +3128,6 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
         launch_chunks = nchunks;
       }
       GDF_TRY(run_scatter());
-      if (chunk_major) {                 // (LAB) the scatter has been timed; the records are not in the layout the aggregation reads
-        HIP_TRY(hipStreamSynchronize(stream0()));
-        *done = false;
-        return GDF_SUCCESS;
-      }
       if (!is_spec) {
         hipLaunchKernelGGL(gb_strided_u32, dim3((P + 256) / 256), dim3(256), 0, stream0(), (const uint32_t *)hist.as<uint32_t>(), d_start.as<uint32_t>(),
                            (int)P + 1, (size_t)nchunks);
@@ -3346,7 +3305,7 @@ static gdf_error gb_path_sorted(GbJob &j, bool *done) {
     {
       const int id_bits = sp.total_bits < GB_PART_ID_BITS ? sp.total_bits : GB_PART_ID_BITS;
       if (sp.ordered && sp.total_bits - id_bits <= GB_PART_MAX_BITS && !lab::path_on("GDF_GB_NO_PART")) {
-        if (sp.total_bits + vbit + null_bit <= 32 && !lab::knob_on("GDF_GB_NO_K32")) return gb_sorted_partitioned<uint32_t>(j, sp, vbit, null_bit, done);
+        if (sp.total_bits + vbit + null_bit <= 32) return gb_sorted_partitioned<uint32_t>(j, sp, vbit, null_bit, done);
         return gb_sorted_partitioned<uint64_t>(j, sp, vbit, null_bit, done);
       }
     }
@@ -3559,7 +3518,7 @@ static gdf_error group_by_hash(int ncols, gdf_column **cols, gdf_column *col_agg
   }
   GbKeyPlan guess_plan{};
   bool guess_plan_ok = false;
-  if (!j.plan.packed && n >= ((int64_t)1 << 24) && !lab::knob_on("GDF_GB_NO_GUESS_RANGES")) {
+  if (!j.plan.packed && n >= ((int64_t)1 << 24)) {
     GDF_TRY(gb_plan_range_sampled(t, &guess_plan, &guess_plan_ok));
     const int vb = (col_agg->valid != nullptr && op != OP_COUNT) ? 1 : 0, nb = t.any_valid ? 1 : 0;
     guess_plan_ok = guess_plan_ok && guess_plan.total_bits >= 18 && guess_plan.total_bits - GB_PART_ID_BITS <= GBP_MAX_PART_BITS &&

@@ -285,12 +285,10 @@ __global__ __launch_bounds__(HP_THREADS) void part_scatter_fast_kernel(const K *
   }
 }
 
-// LDS-regrouped scatter.  Same offsets contract as part_scatter_kernel.  Two shapes:
-//   P <= 256  : 256 threads x 16 rows (4096-row tiles, 41 KB of LDS, several workgroups per CU);
-//   P <= 1024 : 1024 threads x 12 rows (12288-row tiles, 137 KB, one workgroup per CU) -- a (tile, partition) run is still
-//               12 rows = 96 bytes at P = 1024.  The direct scatter that served every fan-out beyond 256 in round 1 issues
-//               one store request per row and column: 4.0 ms per 1e8 rows of (int64, float64, int8) at P = 1000.
-constexpr int HPT_MAX_PARTS = 256;
+// LDS-regrouped scatter.  Same offsets contract as part_scatter_kernel.  One shape is instantiated, for P <= 1024:
+// 1024 threads x 12 rows (12288-row tiles, 137 KB, one workgroup per CU) -- a (tile, partition) run is still 12 rows =
+// 96 bytes at P = 1024.  The direct scatter that served every fan-out beyond 256 in round 1 issues one store request per
+// row and column: 4.0 ms per 1e8 rows of (int64, float64, int8) at P = 1000.
 constexpr int HPT_BIG_PARTS = 1024;
 // TH threads, at most MAXP partitions, FI rows per thread with a directly read key column (half that with the generic row hash:
 // that many generic hashes per thread spill)
@@ -1037,7 +1035,7 @@ __global__ __launch_bounds__(HP_THREADS) void fnv_rows_kernel(FnvCols c, unsigne
 // P=1 0.47 vs 0.84 ms, P=2 0.43 vs 0.52, P=4 0.47 vs 0.37, P=8 0.51 vs 0.36 -- from 4 partitions on the ballots cost
 // more than the conflicts; the scatter pass does not care either way.  -1 = per-lane atomics.
 static int partition_agg_bits(uint32_t P) {
-  if (P > 2 || lab::knob_on("GDF_HP_NO_AGG")) return -1;
+  if (P > 2) return -1;
   int bits = 0;
   while ((1u << bits) < P) ++bits;
   return bits;
@@ -1081,8 +1079,7 @@ static gdf_error hash_partition_two_level(int ncols, gdf_column *input[], const 
   // the smallest shift that leaves at most 1024 super-partitions, raised to the balanced one (K ~ sqrt(P), at most 256 bins at level B)
   int kshift = 0;
   while (((P + (1u << kshift) - 1) >> kshift) > (uint32_t)HPT_BIG_PARTS) ++kshift;
-  if (!lab::knob_on("GDF_HP_MIN_SHIFT"))
-    while (kshift < 8 && (1u << (2 * kshift)) < P) ++kshift;
+  while (kshift < 8 && (1u << (2 * kshift)) < P) ++kshift;
   const uint32_t K = 1u << kshift, S = (P + K - 1) >> kshift;
   const uint32_t pow2mask = (P & (P - 1)) == 0 ? P - 1 : 0;
 
@@ -1348,7 +1345,7 @@ gdf_error gdf_amd_shuffle_partition(gdf_column *keys, int narrow, int64_t lo, in
              (KOUT *)out_keys->data, (int32_t *)out_rows->data);                                                                     \
   HIP_CHECK_LAST();
   // 4-byte output keys and a fan-out of at most 64: the LDS-regrouped scatter (see shuffle_scatter_tile_kernel)
-  const bool tile_scatter = (narrow || win == 4) && P <= (uint32_t)SHT_MAX_PARTS && !lab::knob_on("GDF_HP_NO_SHUFFLE_TILE");
+  const bool tile_scatter = (narrow || win == 4) && P <= (uint32_t)SHT_MAX_PARTS;
   int tile_bits = 0;
   while ((1u << tile_bits) < P) ++tile_bits;
 #define SHUFFLE_TILE_PASSES(KIN)                                                                                                    \
@@ -1484,13 +1481,13 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
   DevBuf hist, starts;
   const bool murmur = hash == GDF_HASH_MURMUR3;
   const int agg_bits = partition_agg_bits(P);
-  const int fastw = (murmur && t.ncols == 1 && (t.col[0].width == 8 || t.col[0].width == 4) && !lab::knob_on("GDF_HP_NO_FAST")) ? t.col[0].width : 0;
+  const int fastw = (murmur && t.ncols == 1 && (t.col[0].width == 8 || t.col[0].width == 4)) ? t.col[0].width : 0;
   // the PAIR kernel (part_scatter_pairs_kernel): one or two 8-byte columns without masks, one of them the hashed key, 16 < P <= 256 --
   // (key, value) tables, the partial aggregates of the distributed group-by.  Its chunks are laid out XCD-major inside a partition.
   // Measured at 1e9 rows x 2 int64 columns, alternating with the generic tile kernel in one process (profiles/r6_m_hash_partition_pairs_ab.jsonl):
   // P = 32 6.38 against 7.08 ms in the scatter kernel, P = 64 7.07 against 7.17, P = 256 8.70 against 8.18 -- at 256 bins its 8192-row tile
   // leaves 32-row runs where the generic kernel's 12288-row single-column stage leaves 48-row ones, and run length wins: up to 64 partitions.
-  bool pairs = fastw == 8 && num_input_cols <= 2 && P > 16 && P <= (uint32_t)lab::knob_int("GDF_HP_PAIRS_MAX", 64) && P <= (uint32_t)HPP_MAX_PARTS &&
+  bool pairs = fastw == 8 && num_input_cols <= 2 && P > 16 && P <= 64 &&
                n >= ((int64_t)1 << 16) && !lab::path_on("GDF_HP_NO_PAIRS");
   for (int i = 0; i < num_input_cols && pairs; ++i)
     pairs = dtype_width(input[i]->dtype) == 8 && !(input[i]->valid && partitioned_output[i]->valid);
@@ -1597,7 +1594,7 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
     pc.dst_map = dst_map.as<uint32_t>();
     if (first > 0)
       hipLaunchKernelGGL(part_apply_map_kernel, dim3(stream_grid(num_rows, HP_THREADS * 4)), dim3(HP_THREADS), 0, stream0(), pc, n);
-    else if (P > 16 && P <= (uint32_t)HPT_BIG_PARTS && !lab::knob_on("GDF_HP_NO_TILE")) {
+    else if (P > 16 && P <= (uint32_t)HPT_BIG_PARTS) {
       // measured at 1e8 rows x 2 int64 columns: P=256 1.47 ms vs 2.83 ms direct; at P=8 the direct kernel's runs are
       // long enough already (1.10 vs 1.19 ms), so small fan-outs keep it
 #define HPT_LAUNCH(MUR, FW, TH, MAXP, FI)                                                                                              \
@@ -1607,21 +1604,12 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
     GDF_LAUNCH("part_scatter", (part_scatter_tile_kernel<MUR, FW, TH, MAXP, FI>), dim3(grid), dim3(TH), tl, stream0(), t, pc, n, chunk, \
                nchunks, P, pow2mask, hist.as<uint32_t>(), PartLevel{});                                                                \
   } while (0)
-      // 12288-row tiles of a 1024-thread workgroup win over 4096-row tiles of 256 threads at EVERY fan-out they share (1e8 rows x
-      // 2 int64 columns, scatter kernel: P = 64 0.73 vs 0.88 ms, P = 256 0.82 vs 1.07 ms): three times the run length.  The small
-      // shape stays behind GDF_HP_BIG_FROM=256
-      const uint32_t big_from = (uint32_t)lab::knob_int("GDF_HP_BIG_FROM", 16);
-      if (P <= big_from && P <= (uint32_t)HPT_MAX_PARTS) {
-        if (fastw == 8) HPT_LAUNCH(true, 8, 256, 256, 16);
-        else if (fastw == 4) HPT_LAUNCH(true, 4, 256, 256, 16);
-        else if (murmur) HPT_LAUNCH(true, 0, 256, 256, 16);
-        else HPT_LAUNCH(false, 0, 256, 256, 16);
-      } else {
-        if (fastw == 8) HPT_LAUNCH(true, 8, 1024, 1024, 12);
-        else if (fastw == 4) HPT_LAUNCH(true, 4, 1024, 1024, 12);
-        else if (murmur) HPT_LAUNCH(true, 0, 1024, 1024, 12);
-        else HPT_LAUNCH(false, 0, 1024, 1024, 12);
-      }
+      // 12288-row tiles of a 1024-thread workgroup: they won over 4096-row tiles of 256 threads at EVERY fan-out the two shared
+      // (1e8 rows x 2 int64 columns, scatter kernel: P = 64 0.73 vs 0.88 ms, P = 256 0.82 vs 1.07 ms): three times the run length
+      if (fastw == 8) HPT_LAUNCH(true, 8, 1024, 1024, 12);
+      else if (fastw == 4) HPT_LAUNCH(true, 4, 1024, 1024, 12);
+      else if (murmur) HPT_LAUNCH(true, 0, 1024, 1024, 12);
+      else HPT_LAUNCH(false, 0, 1024, 1024, 12);
 #undef HPT_LAUNCH
     } else if (fastw == 8)
       GDF_LAUNCH("part_scatter", part_scatter_fast_kernel<uint64_t>, dim3(grid), dim3(HP_THREADS), lds, stream0(), (const uint64_t *)t.col[0].data, pc, n,

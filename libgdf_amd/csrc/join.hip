@@ -48,7 +48,6 @@
 #include "internal.h"
 #include "gdf/gdf_amd_ext.h"
 
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 
@@ -319,6 +318,7 @@ constexpr int JK_MAX_FB = 15;               // 32768 fine partitions: 128 KiB of
 constexpr int JK_HIST_THREADS = 1024;
 constexpr int JK_HIST_ITEMS = 8;
 constexpr int JK_SC_ITEMS = 16;             // tuples per thread per LDS tile; a tile is THREADS * 16 tuples
+constexpr int JK_SC2_THREADS = 256;         // level-2 (and level-3) scatter workgroup: see partition_side
 constexpr int JK_MAX_CHUNKS = 1 << 16;     // level-1 chunks (histogram columns) at most
 constexpr int64_t JK_CHUNK_ROWS = 131072;  // rows per level-1 chunk (swept 8k..512k on C3: profiles/r1_c_sweeps.md)
 constexpr int JK_PROBE_THREADS = 512;
@@ -346,7 +346,7 @@ struct PartGeom {
   int fb, b1, b2;        // fine bits = b1 (level 1) + b2 (level 2)
   int nchunks;           // level-1 chunks (one histogram column each)
   int64_t chunk;         // rows per chunk (multiple of the scatter tile)
-  int dbg;               // experiment switch (env GDF_JK_SDBG), 0 in production
+  int unused;            // always 0: keeps the kernel-argument layout, and with it the kernels' code, as profiled (profiles/lab_removal_isa.md)
   uint64_t kbias;        // added back to a stored key before hashing (= KeyPlan::kmin): partition ids and slots are
                          // functions of the RAW key, so the build-side histogram can run before kmin is known
   // SPECULATIVE layout (cap1 != 0): no histogram pass.  Coarse partition c owns tuples [c * cap1, (c+1) * cap1),
@@ -378,20 +378,7 @@ struct PartGeom {
   // LOCAL partition id is taken from the low word of hash_a * world (uniform inside a rank).  0 / 1: single GPU, the id is
   // hash_a's own top bits.
   uint32_t world;
-#ifdef GDF_AMD_LAB
-  unsigned long long *lab_clock;     // LAB: jk_scatter1 stores the cycles the first / last wave of a workgroup spent in each phase, [chunk][2][8] (knob GDF_JK_CLOCK)
-#endif
 };
-#ifdef GDF_AMD_LAB
-#define LAB_PHASE(i)                                                          \
-  if (g.lab_clock) {                                                          \
-    const unsigned long long lab_now = clock64();                             \
-    lab_ph[i] += (uint32_t)(lab_now - lab_prev);                              \
-    lab_prev = lab_now;                                                       \
-  }
-#else
-#define LAB_PHASE(i)
-#endif
 
 // NARROW: w[i] = key32 << 32 | row, idx unused.  WIDE: w[i] = key64, idx[i] = row.
 // pay (NARROW probe sides of a join that materialises result_cols, see PayCarry): pay[i] = the row's PAYLOAD word -- the
@@ -780,10 +767,8 @@ __device__ __forceinline__ void tile_flush(TileLds<NARROW, THREADS, PAY, ITEMS> 
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      if (LAB_BITS(g.dbg) & 4) dst[u] &= 0xffffu;        // experiment: all stores land in a 512 KiB window
-      if (j0 + u * THREADS < total && !(LAB_BITS(g.dbg) & 1)) {
-        if (LAB_BITS(g.dbg) & 16) __builtin_nontemporal_store(ww[u], out.w + dst[u]);      // experiment: streaming stores (level 2)
-        else out.w[dst[u]] = ww[u];
+      if (j0 + u * THREADS < total) {
+        out.w[dst[u]] = ww[u];
         if (!NARROW) out.idx[dst[u]] = ii[u];
         if constexpr (PAY == 2) *reinterpret_cast<ulonglong2 *>(out.pay + 2 * (size_t)dst[u]) = ulonglong2{pp[u], pq[u]};
         else if (PAY) out.pay[dst[u]] = pp[u];
@@ -896,10 +881,6 @@ __global__ __launch_bounds__(THREADS) void jk_scatter1(KeyTable t, KeyPlan plan,
     okmask &= validbits;
   };
   if (FAST) consume(begin);
-#ifdef GDF_AMD_LAB
-  uint32_t lab_ph[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long lab_prev = g.lab_clock ? clock64() : 0;
-#endif
   for (uint32_t tile = begin; tile < end; tile += JK_TILE) {        // end + JK_TILE < 2^32
     if (!FAST) {
       uint64_t k64[ITEMS];
@@ -939,7 +920,6 @@ __global__ __launch_bounds__(THREADS) void jk_scatter1(KeyTable t, KeyPlan plan,
     for (int k = 0; k < ITEMS; ++k)      // sixteen atomics in flight, one wait
       binrank[k] = (binrank[k] << 16) | atomicAdd(&s.hist[binrank[k]], 1u);
     block_sync();
-    LAB_PHASE(0)       // hash + rank
     uint32_t claimed = 0;
     {
       const uint32_t tid = opaque_tid();
@@ -960,7 +940,6 @@ __global__ __launch_bounds__(THREADS) void jk_scatter1(KeyTable t, KeyPlan plan,
       block_sync();
       claimed = base;
     }
-    LAB_PHASE(1)       // claim issue + scan
     const uint32_t wtid = opaque_tid();
     constexpr int RG = ITEMS % 8 == 0 ? 8 : 6;
 #pragma unroll
@@ -1006,10 +985,8 @@ __global__ __launch_bounds__(THREADS) void jk_scatter1(KeyTable t, KeyPlan plan,
     }
     const bool more = tile + JK_TILE < end;
     __builtin_amdgcn_sched_barrier(0);         // keep the prefetch BELOW the regroup: hoisted, its 32 registers spill
-    LAB_PHASE(2)       // regroup (LDS writes issued) + claim answer
     if (FAST && more) prefetch(tile + JK_TILE);
     block_sync();
-    LAB_PHASE(3)       // prefetch issue + barrier (the regroup's LDS writes land here)
     if (g.cap1 && s.total_abort) return;       // workgroup-uniform (read after the barrier)
     // flush: JK_SC_ITEMS unconditional stores per thread (dead slots -> this thread's dump slot), four at a time to
     // keep the register count under the 128 a 1024-thread workgroup gets (the prefetched keys stay in registers)
@@ -1073,11 +1050,8 @@ __global__ __launch_bounds__(THREADS) void jk_scatter1(KeyTable t, KeyPlan plan,
 #pragma unroll
       for (int k = 0; k < GROUP; ++k) {
         const uint32_t j = ftid + (h * GROUP + k) * THREADS;
-        uint32_t dst = j < total ? gb[k] + j : g.dump + ftid;
-        if (LAB_BITS(g.dbg) & 4) dst &= 0xffffu;           // experiment: all stores land in a 512 KiB window
-        if (LAB_BITS(g.dbg) & 1) dst = g.dump + ftid;      // experiment: no useful stores
-        if (LAB_BITS(g.dbg) & 8) __builtin_nontemporal_store(ww[k], out.w + dst);      // experiment: streaming stores (level 1)
-        else out.w[dst] = ww[k];
+        const uint32_t dst = j < total ? gb[k] + j : g.dump + ftid;
+        out.w[dst] = ww[k];
         if (!NARROW) out.idx[dst] = ii[k];
       }
       __builtin_amdgcn_sched_barrier(0);       // one group's LDS reads at a time: hoisted together they spill
@@ -1085,15 +1059,9 @@ __global__ __launch_bounds__(THREADS) void jk_scatter1(KeyTable t, KeyPlan plan,
     }
     // the stores above stay in flight: this waits for the LOADS only.  Unconditional: keeping the old keys alive for the
     // `no more tiles` case would cost 16 registers across the flush
-    LAB_PHASE(4)       // flush: LDS reads + store issue
     if (FAST) consume(tile + JK_TILE);
     __builtin_amdgcn_sched_barrier(0);         // narrow the keys HERE: sunk into the next ranking, the 64-bit words stay live
-    LAB_PHASE(5)       // wait for the next tile's keys
   }
-#ifdef GDF_AMD_LAB
-  if (g.lab_clock && (threadIdx.x == 0 || threadIdx.x == THREADS - 64))
-    for (int i = 0; i < 6; ++i) g.lab_clock[((size_t)blockIdx.x * 2 + (threadIdx.x ? 1 : 0)) * 8 + i] = lab_ph[i];
-#endif
 }
 
 // 2b. level-1 scatter of a probe side that CARRIES A PAYLOAD (Tuples::pay, PayCarry): one FAST key column without a mask,
@@ -1666,7 +1634,7 @@ struct ProbeArgs {
   uint8_t *build_matched;       // FULL: byte per build ROW, set when matched (may be null)
   uint64_t *counts;             // COUNT pass output / WRITE pass: exclusive offsets
   int32_t *out_probe; int32_t *out_build;
-  int dbg;                      // experiment switch (env GDF_JK_DBG), 0 in production
+  int unused;                   // always 0: keeps the kernel-argument layout, see PartGeom::unused
   uint64_t kbias;               // see PartGeom::kbias
   int optimistic;               // WRITE pass without a count pass: unit u may write at most probe_count pairs
   unsigned long long *opt_state; // [0] = pairs written by all units, [1] = some unit needed more room,
@@ -1817,7 +1785,7 @@ __global__ __launch_bounds__(JK_PROBE_THREADS) void jk_probe(ProbeArgs a, KeyTab
     if (moves == JK_CUCKOO_MAX_MOVES) *l.cuckoo_failed = 1;   // `cur` is homeless: rebuild below
   }
   block_sync();
-  const bool cuckoo = *l.cuckoo_failed == 0 && !(LAB_BITS(a.dbg) & 8);
+  const bool cuckoo = *l.cuckoo_failed == 0;
   if (!cuckoo) {
     // ---- multimap rebuild over the same 2*H slots: open addressing over the DISTINCT keys, every key's tuples chained
     // behind the one that took the slot (next[]).  Round 1 gave every tuple a slot of its own: a key that occurs four times
@@ -1851,7 +1819,6 @@ __global__ __launch_bounds__(JK_PROBE_THREADS) void jk_probe(ProbeArgs a, KeyTab
     if (!WRITE && a.opt_state && threadIdx.x == 0 && dup_seen) atomicAdd(&a.opt_state[3], 1ull);
   }
 
-  if (LAB_BITS(a.dbg) & 128) return;      // experiment: build phase only
   // optimistic pass: the unit owns exactly probe_count output slots starting at its offset
   const unsigned long long unit_base = WRITE ? a.counts[uid] : 0ull;
   const unsigned long long unit_end = (WRITE && a.optimistic) ? unit_base + u.probe_count : ~0ull;
@@ -1913,7 +1880,6 @@ __global__ __launch_bounds__(JK_PROBE_THREADS) void jk_probe(ProbeArgs a, KeyTab
         const uint64_t raw = k[b] + a.kbias;
         pa[b] = l.T[hash_a(raw) & (H - 1)];
         pb[b] = l.T[H + (hash_b(raw) & (H - 1))];
-        if (LAB_BITS(a.dbg) & 64) { pa[b] = (uint32_t)k[b] & 1023u; pb[b] = JK_NOPOS; }      // experiment: no table lookups
       }
       uint64_t ka[NB], kb[NB];
 #pragma unroll
@@ -1995,7 +1961,6 @@ __global__ __launch_bounds__(JK_PROBE_THREADS) void jk_probe(ProbeArgs a, KeyTab
           a.out_build[pos] = JK_EMPTY;
           pay_gather(a, pos, prow[b]);
         } else if (c >= 1 && (cuckoo || c == 1)) {
-          if (LAB_BITS(a.dbg) & 32) continue;                  // experiment: no output stores
           a.out_probe[pos] = prow[b];
           a.out_build[pos] = build_row<NARROW>(l, hit_a[b]);
           pay_gather(a, pos, prow[b]);
@@ -2152,7 +2117,7 @@ __global__ __launch_bounds__(JK_PROBE_THREADS) void jk_probe_fast(ProbeArgs a) {
     seed += 0x9e3779b9u;
     block_sync();
   }
-  if (*l.cuckoo_failed | (unsigned)(LAB_BITS(a.dbg) & 8)) {
+  if (*l.cuckoo_failed) {
     if (threadIdx.x == 0) a.unit_todo[atomicAdd(&a.opt_state[2], 1ull)] = blockIdx.x;
     return;
   }
@@ -2253,7 +2218,7 @@ __global__ __launch_bounds__(JK_PROBE_THREADS) void jk_probe_fast(ProbeArgs a) {
     auto emit = [&](int b, uint32_t pos, uint32_t c) {
       const bool ha = (hamask >> b) & 1u, pad = (padmask >> b) & 1u;
       if (pos + c > unit_cap) a.opt_state[1] = 1;   // would spill into the next unit's slots: the host redoes the join two-pass
-      else if (!(LAB_BITS(a.dbg) & 32)) {
+      else {
         // build row of a hit: NARROW carries it in the low half of the staged word, WIDE reads it from the staged row numbers
         // (WIDE: the second row of a tuple with two hits is read under c == 2 only -- as a value selected next to hitrow[b] the
         // compiler issued the read for every emitted tuple, one LDS round trip each)
@@ -2277,7 +2242,7 @@ __global__ __launch_bounds__(JK_PROBE_THREADS) void jk_probe_fast(ProbeArgs a) {
         }
       }
     };
-    if (__all((hamask & hbmask) == 0) && !(LAB_BITS(a.dbg) & 2048)) {      // (GDF_JK_DBG=2048: one claim per tuple, as before)
+    if (__all((hamask & hbmask) == 0)) {
       // nobody has two pairs for one tuple (no key sits in both tables: the usual case).  ONE claim per wave and batch: the NB
       // ballots give every tuple its offset inside the wave's range, lane 0 claims the sum, and the base comes back through
       // readfirstlane -- per tuple a claim + a bpermute were two LDS round trips, sixteen per batch, on the critical path of a
@@ -2425,7 +2390,7 @@ __global__ __launch_bounds__(JK_PROBE_THREADS) void jk_count_fast(ProbeArgs a) {
     seed += 0x9e3779b9u;
     block_sync();
   }
-  if (*l.cuckoo_failed | (unsigned)(LAB_BITS(a.dbg) & 8)) {
+  if (*l.cuckoo_failed) {
     if (threadIdx.x == 0) a.unit_todo[atomicAdd(&a.opt_state[2], 1ull)] = blockIdx.x;
     return;
   }
@@ -3208,17 +3173,15 @@ struct SideBufs {            // partitioned tuples of one relation
 
 static PartGeom choose_geometry(int64_t build_rows) {
   PartGeom g{};
-  g.dbg = (int)lab::knob_int("GDF_JK_SDBG", 0);
   int fb = 0;
   while (fb < JK_MAX_FB && (build_rows >> fb) > JK_TARGET_BUILD) ++fb;
   // never fewer than 32 partitions: with one or a few, every tuple of a tile ranks on the same LDS counter and the
   // probe side has to take the histogram pass (5e8 x 3000 rows: 8.0 ms with one partition, see the notes in profiles/)
-  if (fb < 5 && !lab::knob_on("GDF_JK_ALLOW_FEW_PARTS")) fb = 5;
+  if (fb < 5) fb = 5;
   // (test hook: the geometry of a large build relation on a small one -- the six-byte tuples need 2^15 partitions)
   if (const long long forced = lab::path_int("GDF_JK_FORCE_FB", 0)) { if (forced >= 5 && forced <= JK_MAX_FB) fb = (int)forced; }
   g.fb = fb;
   g.b1 = fb <= 8 ? fb : (fb + 1) / 2;
-  if (lab::knob_on("GDF_JK_B1") && fb > 8) { const int b1 = (int)lab::knob_int("GDF_JK_B1", 0); if (b1 >= fb - 8 && b1 <= 8) g.b1 = b1; }   // experiment switch
   g.b2 = fb - g.b1;
   // more rows than 2^15 LDS-sized partitions hold: a third level (at most 256-way), decided here, applied by refine_side
   g.b3 = 0;
@@ -3238,21 +3201,21 @@ static gdf_error launch_scatter1_t(const KeyTable &t, const KeyPlan &plan, const
   HIP_CHECK_LAST();
   return GDF_SUCCESS;
 }
+// threads of a level-1 scatter workgroup (swept on C3: profiles/r1_c_sweeps.md).  WIDE tuples from one 8-byte key column take the
+// 1024-thread tile with twelve tuples per thread, sc1_items -- 16384 x 12 B would not fit 160 KiB
+static constexpr int sc1_threads(bool narrow, int fast) { return (narrow || fast == 8) ? 1024 : 512; }
 template <int FAST, bool NARROW, bool MASKED>
-static gdf_error launch_scatter1_n(int threads, const KeyTable &t, const KeyPlan &plan, const PartGeom &g, const uint32_t *H1off, Tuples out) {
-  if (threads == 1024) { if constexpr (NARROW || FAST == 8) return launch_scatter1_t<FAST, NARROW, 1024, MASKED>(t, plan, g, H1off, out); }
-  if (threads >= 512) return launch_scatter1_t<FAST, NARROW, 512, MASKED>(t, plan, g, H1off, out);
-  if constexpr (MASKED) return launch_scatter1_t<FAST, NARROW, 512, MASKED>(t, plan, g, H1off, out);      // (masked: the two production tile sizes only)
-  else return launch_scatter1_t<FAST, NARROW, 256, MASKED>(t, plan, g, H1off, out);
+static gdf_error launch_scatter1_n(const KeyTable &t, const KeyPlan &plan, const PartGeom &g, const uint32_t *H1off, Tuples out) {
+  return launch_scatter1_t<FAST, NARROW, sc1_threads(NARROW, FAST), MASKED>(t, plan, g, H1off, out);
 }
-static gdf_error launch_scatter1(int fast, bool narrow, int threads, const KeyTable &t, const KeyPlan &plan, const PartGeom &g,
+static gdf_error launch_scatter1(int fast, bool narrow, const KeyTable &t, const KeyPlan &plan, const PartGeom &g,
                                  const uint32_t *H1off, Tuples out, bool l6 = false) {
   const bool masked = fast != 0 && t.col[0].valid != nullptr;
   if (l6) {                          // six-byte level-1 tuples (L6): NARROW, a FAST key column, the 1024-thread tile, speculative layout
     // (TWO workgroups of half-size tiles per CU -- what a software-pipelined workgroup, VERDICT r4 item 1, comes down to in 135 KB of
     // LDS -- were built as a LAB variant in round 5 and lost: jk_scatter1 2.97 - 2.98 against 2.87 - 2.91 ms for C3's probe side in
     // alternating processes, profiles/r5_c_half_tile_workgroups_ab.jsonl; the variant is gone again)
-    if (!(fast && threads == 1024 && g.cap1 && g.xs == 6 && g.b1 == 8) || (!narrow && fast != 8)) return GDF_INVALID_API_CALL;
+    if (!(fast && g.cap1 && g.xs == 6 && g.b1 == 8) || (!narrow && fast != 8)) return GDF_INVALID_API_CALL;
     if (!narrow) {                   // WIDE keys: the ten-byte tuples (W10, p10_key) -- 12 tuples per thread, 12 bytes per tuple in LDS
       const size_t lds = sizeof(TileLds<false, 1024, false, 12>);
       if (masked) {
@@ -3280,15 +3243,15 @@ static gdf_error launch_scatter1(int fast, bool narrow, int threads, const KeyTa
     return GDF_SUCCESS;
   }
   if (masked) {
-    if (fast == 4) return launch_scatter1_n<4, true, true>(threads, t, plan, g, H1off, out);
-    return narrow ? launch_scatter1_n<8, true, true>(threads, t, plan, g, H1off, out)
-                  : launch_scatter1_n<8, false, true>(threads, t, plan, g, H1off, out);
+    if (fast == 4) return launch_scatter1_n<4, true, true>(t, plan, g, H1off, out);
+    return narrow ? launch_scatter1_n<8, true, true>(t, plan, g, H1off, out)
+                  : launch_scatter1_n<8, false, true>(t, plan, g, H1off, out);
   }
-  if (fast == 4) return launch_scatter1_n<4, true, false>(threads, t, plan, g, H1off, out);      // 4-byte keys are always narrow
-  if (fast == 8) return narrow ? launch_scatter1_n<8, true, false>(threads, t, plan, g, H1off, out)
-                               : launch_scatter1_n<8, false, false>(threads, t, plan, g, H1off, out);
-  return narrow ? launch_scatter1_n<0, true, false>(threads, t, plan, g, H1off, out)
-                : launch_scatter1_n<0, false, false>(threads, t, plan, g, H1off, out);
+  if (fast == 4) return launch_scatter1_n<4, true, false>(t, plan, g, H1off, out);      // 4-byte keys are always narrow
+  if (fast == 8) return narrow ? launch_scatter1_n<8, true, false>(t, plan, g, H1off, out)
+                               : launch_scatter1_n<8, false, false>(t, plan, g, H1off, out);
+  return narrow ? launch_scatter1_n<0, true, false>(t, plan, g, H1off, out)
+                : launch_scatter1_n<0, false, false>(t, plan, g, H1off, out);
 }
 // 8 / 4: the relation is one raw integer / float column of that width, with or without a validity mask (direct column
 // reads, the mask read paired with the data: jk_scatter1<MASKED>, fetch_keys); 0: generic key construction
@@ -3313,21 +3276,13 @@ static gdf_error launch_scatter2_t(uint32_t ntiles, const PartGeom &g, Level2Map
   HIP_CHECK_LAST();
   return GDF_SUCCESS;
 }
-static gdf_error launch_scatter2(bool narrow, int threads, uint32_t ntiles, const PartGeom &g, Level2Map m, Tuples in,
+static gdf_error launch_scatter2(bool narrow, uint32_t ntiles, const PartGeom &g, Level2Map m, Tuples in,
                                  uint32_t *cursor, Tuples out, bool p6 = false, bool in6 = false, int pw = 1) {
   if (in6) {                         // six-byte level-1 tuples in, six-byte level-2 tuples out
     if (!(p6 && !m.keys32 && g.b1 == 8)) return GDF_INVALID_API_CALL;
     m.ntiles = ntiles;
     m.xcd_order = (ntiles >= 64 && !lab::path_on("GDF_JK_NO_XCD_ORDER")) ? 1 : 0;
     const uint32_t grid = sc2_grid(m, ntiles);
-    if (!narrow && lab::knob_int("GDF_JK_W10_SC2_THREADS", 0) == 512) {      // experiment: the same 4096-tuple tile under 512 threads
-      using Tile = TileLds<false, 512, false, 8>;
-      const size_t lds = offsetof(Tile, cursor);
-      HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<false, 512, false, true, false, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      GDF_LAUNCH("jk_scatter2_w10", (jk_scatter2<false, 512, false, true, false, true, 8>), dim3(grid), dim3(512), lds, stream0(), g, m, in, cursor, out);
-      HIP_CHECK_LAST();
-      return GDF_SUCCESS;
-    }
     if (!narrow) {                   // ten-byte tuples in and out (WIDE keys)
       const size_t lds = level2_lds_bytes<false, 256>();
       HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<false, 256, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -3390,13 +3345,8 @@ static gdf_error launch_scatter2(bool narrow, int threads, uint32_t ntiles, cons
     HIP_CHECK_LAST();
     return GDF_SUCCESS;
   }
-  if (narrow) {
-    if (threads == 1024) return launch_scatter2_t<true, 1024>(ntiles, g, m, in, cursor, out);
-    if (threads == 512) return launch_scatter2_t<true, 512>(ntiles, g, m, in, cursor, out);
-    return launch_scatter2_t<true, 256>(ntiles, g, m, in, cursor, out);
-  }
-  if (threads >= 512) return launch_scatter2_t<false, 512>(ntiles, g, m, in, cursor, out);
-  return launch_scatter2_t<false, 256>(ntiles, g, m, in, cursor, out);
+  if (narrow) return launch_scatter2_t<true, JK_SC2_THREADS>(ntiles, g, m, in, cursor, out);
+  return launch_scatter2_t<false, JK_SC2_THREADS>(ntiles, g, m, in, cursor, out);
 }
 
 // partitions one relation into g.fb-bit fine partitions
@@ -3422,12 +3372,6 @@ static gdf_error launch_scatter1_pay(int fast, int pmode, const KeyTable &t, con
   return GDF_SUCCESS;
 }
 
-static int level2_threads(int sc_threads) {
-  const int env = (int)lab::knob_int("GDF_JK_SC2_THREADS", 0);
-  if (env == 256 || env == 512 || env == 1024) return env < sc_threads ? env : sc_threads;
-  return sc_threads > 256 ? 256 : sc_threads;
-}
-
 // pay (may be null) + pmode: the relation carries a payload word per row (PayCarry); NARROW tuples and a FAST key column only
 // keep_running (with device_index: a BUILD side of the main path): nothing waits for the last launches -- the scratch they use goes to
 // sb->hold, the caller settles it (SideBufs::settle) once the stream has been synchronised for some other reason
@@ -3438,8 +3382,7 @@ static gdf_error partition_side(const KeyTable &t, KeyPlan &plan, PartGeom g, Si
   // Chunks are SMALL (a few tiles) and processed in blockIdx order, so that the workgroups resident at
   // any moment write into a narrow window of every partition's output range: with a few thousand
   // 2 MiB pages live the scatter ran ~1.5x slower per row at 1e9 rows than at 5e8 (TLB reach).
-  const int64_t chunk_rows_env = lab::knob_int("GDF_JK_CHUNK_ROWS", 0);
-  int64_t chunk = chunk_rows_env ? chunk_rows_env : JK_CHUNK_ROWS;
+  int64_t chunk = JK_CHUNK_ROWS;
   if (n / chunk > JK_MAX_CHUNKS) chunk = (n + JK_MAX_CHUNKS - 1) / JK_MAX_CHUNKS;
   constexpr int64_t MAX_TILE = 1024 * JK_SC_ITEMS;      // chunks are whole tiles for every tile size in use
   chunk = ((chunk + MAX_TILE - 1) / MAX_TILE) * MAX_TILE;
@@ -3462,7 +3405,7 @@ static gdf_error partition_side(const KeyTable &t, KeyPlan &plan, PartGeom g, Si
   HIP_TRY(hipFuncSetAttribute((const void *)jk_hist<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
   HIP_TRY(hipFuncSetAttribute((const void *)jk_hist<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
   long long *d_mm = nullptr;
-  if (decide_narrow && !lab::knob_on("GDF_JK_WIDE"))         // GDF_JK_WIDE: experiment switch, force 12-byte tuples
+  if (decide_narrow)
     d_mm = reinterpret_cast<long long *>(fine_hist.as<uint32_t>() + nfine);
   if (fast == 8)
     GDF_LAUNCH("jk_hist", jk_hist<8>, dim3(hist_grid), dim3(JK_HIST_THREADS), hist_lds, stream0(), t, plan, g,
@@ -3521,17 +3464,10 @@ static gdf_error partition_side(const KeyTable &t, KeyPlan &plan, PartGeom g, Si
   g.kbias = plan.kmin;
   // scatter tile: THREADS * 16 tuples regrouped in LDS per step.  Bigger tiles mean longer runs per
   // (tile, bin) -- DRAM-friendlier writes -- at the price of fewer resident workgroups.
-  const int sc_threads_env = (int)lab::knob_int("GDF_JK_SC_THREADS", 0);
-  // (WIDE tuples from one 8-byte key column: the 1024-thread tile with twelve tuples per thread, sc1_items -- 16384 x 12 B would not
-  // fit 160 KiB; round 6, 512 threads before: C3's wide build side 0.64 ms in jk_scatter1)
-  int sc_threads = sc_threads_env ? sc_threads_env : ((narrow || (fast == 8 && !lab::knob_on("GDF_JK_WIDE_512"))) ? 1024 : 512);   // swept on C3: profiles/r1_c_sweeps.md
-  if (sc_threads != 256 && sc_threads != 512 && sc_threads != 1024) sc_threads = 256;
-  if (!narrow && fast != 8 && sc_threads == 1024) sc_threads = 512;
   // a payload word only travels with NARROW tuples from a FAST, unmasked key column (jk_scatter1_pay); a build side that turns out
   // otherwise simply does not carry it (sb->pay stays empty and the caller gathers)
   if (pay && !(narrow && fast && !t.col[0].valid)) pay = nullptr;
-  const int sc2_threads = pay ? 256 : level2_threads(sc_threads);
-  const int64_t JK_TILE2 = (int64_t)sc2_threads * (pay ? JK_PAY_ITEMS : JK_SC_ITEMS);
+  const int64_t JK_TILE2 = (int64_t)JK_SC2_THREADS * (pay ? JK_PAY_ITEMS : JK_SC_ITEMS);
 
   // + 2: the probe kernel's last 16-byte load may touch one tuple past the end; + 1024: jk_scatter1's per-thread dump slots
   g.dump = (uint32_t)(cap + 2);
@@ -3572,18 +3508,18 @@ static gdf_error partition_side(const KeyTable &t, KeyPlan &plan, PartGeom g, Si
     }
     // (a probe side on the exact layout -- skewed probe keys -- writes six-byte tuples as the speculative layout does, see p6_store)
     // (WIDE keys: ten-byte tuples, the key's high words in idx[] -- p10_key)
-    p6 = want_p6 && !pay && sc2_threads == 256;
+    p6 = want_p6 && !pay;
     RMM_TRY(sb->w[1].alloc(p6 ? 6 * (cap + 2) + 16 : sizeof(uint64_t) * (cap + 2)));
     if (!narrow) RMM_TRY(sb->idx[1].alloc(sizeof(int32_t) * (cap + 2)));     // + 2: the lean probe kernel reads row numbers in pairs
     if (pay) RMM_TRY(sb->pay[1].alloc(sizeof(uint64_t) * pw * (cap + 2)));
   }
   if (pay) GDF_TRY(launch_scatter1_pay(fast, pmode, t, plan, g, H1.as<uint32_t>(), *pay, t0));
-  else GDF_TRY(launch_scatter1(fast, narrow, sc_threads, t, plan, g, H1.as<uint32_t>(), t0));
+  else GDF_TRY(launch_scatter1(fast, narrow, t, plan, g, H1.as<uint32_t>(), t0));
   HIP_CHECK_LAST();
   sb->final_buf = 0;
   if (level2) {
     Level2Map m{d_coarse.as<uint32_t>(), d_coarse.as<uint32_t>() + 1, d_tiles.as<uint32_t>()};
-    if (ntiles) GDF_TRY(launch_scatter2(narrow, sc2_threads, ntiles, g, m, sb->tuples(0), cursor.as<uint32_t>(), sb->tuples(1), p6, false, pw));
+    if (ntiles) GDF_TRY(launch_scatter2(narrow, ntiles, g, m, sb->tuples(0), cursor.as<uint32_t>(), sb->tuples(1), p6, false, pw));
     HIP_CHECK_LAST();
     if (keep_running && device_index) {          // (no host vector is in flight on this path)
       for (DevBuf *b : {&sb->w[0], &sb->idx[0], &sb->pay[0], &d_coarse, &d_tiles, &cursor, &H1, &fine_hist, &scan_a, &scan_b}) sb->keep(*b);
@@ -3628,8 +3564,7 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
   if (app) g.row_base = (int32_t)app->rows;
   const int64_t n = t.nrows;
   const bool narrow = plan.narrow != 0;
-  const int64_t chunk_rows_env = lab::knob_int("GDF_JK_CHUNK_ROWS", 0);
-  int64_t chunk = chunk_rows_env ? chunk_rows_env : JK_CHUNK_ROWS;
+  int64_t chunk = JK_CHUNK_ROWS;
   if (n / chunk > JK_MAX_CHUNKS) chunk = (n + JK_MAX_CHUNKS - 1) / JK_MAX_CHUNKS;
   constexpr int64_t MAX_TILE = 1024 * JK_SC_ITEMS;
   chunk = ((chunk + MAX_TILE - 1) / MAX_TILE) * MAX_TILE;
@@ -3638,18 +3573,14 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
   if (g.nchunks == 0) g.nchunks = 1;
   const uint32_t nfine = 1u << g.fb, ncoarse = 1u << g.b1;
   const int fast = fast_key_width(t, plan);
-  const int sc_threads_env = (int)lab::knob_int("GDF_JK_SC_THREADS", 0);
   // TEN-BYTE level-1 tuples for WIDE keys (W10, see p10_key): the conditions of the six-byte ones below on an 8-byte key column; the
   // level-1 tile is then 1024 threads x 12 tuples (decided here: the tile size goes into the buffer sizes)
-  const bool w10 = want_p6 && defer && !app && !narrow && !pay && fast == 8 && !sc_threads_env && g.b1 == 8 && g.b2 > 0 && chunk == ((int64_t)1 << 17) &&
+  const bool w10 = want_p6 && defer && !app && !narrow && !pay && fast == 8 && g.b1 == 8 && g.b2 > 0 && chunk == ((int64_t)1 << 17) &&
                    n < (((int64_t)1 << 30) - ((int64_t)1 << 23)) && g.row_base == 0 &&
                    ((n >= ((int64_t)1 << 26) && !lab::path_on("GDF_JK_NO_XCD_SPLIT")) || lab::path_on("GDF_JK_FORCE_L6")) && !lab::path_on("GDF_JK_NO_L6");
-  int sc_threads = sc_threads_env ? sc_threads_env : ((narrow || w10 || (fast == 8 && !lab::knob_on("GDF_JK_WIDE_512"))) ? 1024 : 512);
-  if (sc_threads != 256 && sc_threads != 512 && sc_threads != 1024) sc_threads = 256;
-  if (!narrow && fast != 8 && sc_threads == 1024) sc_threads = 512;
+  const int sc_threads = sc1_threads(narrow, fast);
   const int64_t JK_TILE = (int64_t)sc_threads * sc1_items(narrow, sc_threads);
-  const int sc2_threads = pay ? 256 : level2_threads(sc_threads);
-  const int64_t JK_TILE2 = (int64_t)sc2_threads * (pay ? JK_PAY_ITEMS : JK_SC_ITEMS);
+  const int64_t JK_TILE2 = (int64_t)JK_SC2_THREADS * (pay ? JK_PAY_ITEMS : JK_SC_ITEMS);
   auto room = [dup](double mean, uint32_t align) {
     const double c = mean + 8.0 * std::sqrt(mean * (1.0 + dup)) + 64.0;
     return (uint32_t)(((uint64_t)c + align - 1) / align * align);
@@ -3661,7 +3592,7 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
   // 1024-thread tile, 256 coarse partitions (24 hash bits left), chunks of exactly 2^17 rows and 64 regions per coarse partition
   // (the row number's bits 17..22), rows below 2^30 - 2^23 (seven explicit high bits, and the all-ones tuple stays free for padding).
   // GDF_JK_FORCE_L6: test switch, small relations too (their few chunks number the regions all the same); GDF_JK_NO_L6: off
-  const bool l6 = w10 || (want_p6 && defer && !app && narrow && !pay && fast != 0 && sc_threads == 1024 && sc2_threads == 256 && g.b1 == 8 && g.b2 > 0 &&
+  const bool l6 = w10 || (want_p6 && defer && !app && narrow && !pay && fast != 0 && g.b1 == 8 && g.b2 > 0 &&
                           chunk == ((int64_t)1 << 17) && n < (((int64_t)1 << 30) - ((int64_t)1 << 23)) && g.row_base == 0 &&
                           (g.xs == 3 || lab::path_on("GDF_JK_FORCE_L6")) && !lab::path_on("GDF_JK_NO_L6"));
   if (l6) g.xs = 6;
@@ -3741,35 +3672,26 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
   const size_t bytes1 = l6 ? 6 * ((size_t)size1 + 2048) + 16 : sizeof(uint64_t) * size1;
   const size_t bytes1_hi = sizeof(int32_t) * ((size_t)size1 + (l6 ? 2048 : 0));      // (W10: the high words, dump slots as in w[0])
   // (place_draws_now: the call's budget for candidates, internal.h -- once it is spent the pool is asked to HOLD its champions)
-  const bool calibrate = !lab::knob_on("GDF_JK_NO_CALIBRATE");
-  if (placed) RMM_TRY(sb->w[0].alloc_placed(JK_ROLE_LEVEL1, bytes1, calibrate ? place_draws_now(JK_PLACE_DRAWS) : JK_PLACE_DRAWS));
+  if (placed) RMM_TRY(sb->w[0].alloc_placed(JK_ROLE_LEVEL1, bytes1, place_draws_now(JK_PLACE_DRAWS)));
   else RMM_TRY(sb->w[0].alloc(bytes1));      // (L6: + two dump slots per thread behind the regions)
   if (hi_placed1) RMM_TRY(sb->idx[0].alloc_placed(JK_ROLE_LEVEL1_HI, bytes1_hi, -1));      // (held while the six-byte stream's block is chosen)
   else if (!narrow) RMM_TRY(sb->idx[0].alloc(bytes1_hi));
   const int pw = pay ? pay_words(pmode) : 1;
   sb->pay_words = pw;
   if (pay) RMM_TRY(sb->pay[0].alloc(sizeof(uint64_t) * pw * size1));
-#ifdef GDF_AMD_LAB
-  DevBuf lab_clk;
-  if (lab::knob_on("GDF_JK_CLOCK") && !pay) {
-    RMM_TRY(lab_clk.alloc(sizeof(unsigned long long) * 16 * (size_t)g.nchunks));
-    HIP_TRY(hipMemsetAsync(lab_clk.p, 0, sizeof(unsigned long long) * 16 * (size_t)g.nchunks, stream0()));
-    g.lab_clock = lab_clk.as<unsigned long long>();
-  }
-#endif
   // PLACEMENT TOURNAMENT of the level-1 buffer (round 5).  jk_scatter1 runs in one of two modes on a given physical placement of this
   // buffer (2.9 or 3.3 ms for C3's probe side), and most fresh blocks are slow ones.  While the pool is still comparing
   // placements for this (role, size) -- the first call of a shape -- every candidate block is timed on a CALIBRATION run, the real kernel
   // over the first quarter of the chunks (every region's write front opens, ~0.8 ms), and handed back with that time; the pool keeps
   // the fastest of JK_PLACE_DRAWS + 1 and this call, and every later one, runs on it.  ~2 ms per candidate, once per shape.
-  if (placed && calibrate) {
+  if (placed) {
     for (int round = 0; round <= JK_PLACE_DRAWS && sb->w[0].measure; ++round) {
       PlaceRound charge;
       PartGeom gc = g;
       gc.nchunks = std::max(1, g.nchunks / 4);
       sb->w[0].clock_begin(stream0());
       if (pay) GDF_TRY(launch_scatter1_pay(fast, pmode, t, plan, gc, nullptr, *pay, sb->tuples(0)));
-      else GDF_TRY(launch_scatter1(fast, narrow, sc_threads, t, plan, gc, nullptr, sb->tuples(0), l6));
+      else GDF_TRY(launch_scatter1(fast, narrow, t, plan, gc, nullptr, sb->tuples(0), l6));
       sb->w[0].clock_end(stream0());
       HIP_TRY(hipMemsetAsync(spec.p, 0, sizeof(uint32_t) * (nseg + 1), stream0()));
       RMM_TRY(sb->w[0].alloc_placed(JK_ROLE_LEVEL1, bytes1, place_draws_now(JK_PLACE_DRAWS)));      // (reset() reports the time; the champion or the next challenger comes back)
@@ -3784,7 +3706,7 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
       PartGeom gc = g;
       gc.nchunks = std::max(1, g.nchunks / 4);
       sb->idx[0].clock_begin(stream0());
-      GDF_TRY(launch_scatter1(fast, narrow, sc_threads, t, plan, gc, nullptr, sb->tuples(0), l6));
+      GDF_TRY(launch_scatter1(fast, narrow, t, plan, gc, nullptr, sb->tuples(0), l6));
       sb->idx[0].clock_end(stream0());
       HIP_TRY(hipMemsetAsync(spec.p, 0, sizeof(uint32_t) * (nseg + 1), stream0()));
       RMM_TRY(sb->idx[0].alloc_placed(JK_ROLE_LEVEL1_HI, bytes1_hi, place_draws_now(JK_PLACE_DRAWS)));
@@ -3799,33 +3721,8 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
   }
   sb->w[0].clock_begin(stream0());
   if (pay) GDF_TRY(launch_scatter1_pay(fast, pmode, t, plan, g, nullptr, *pay, sb->tuples(0)));
-  else GDF_TRY(launch_scatter1(fast, narrow, sc_threads, t, plan, g, nullptr, sb->tuples(0), l6));
+  else GDF_TRY(launch_scatter1(fast, narrow, t, plan, g, nullptr, sb->tuples(0), l6));
   sb->w[0].clock_end(stream0());
-#ifdef GDF_AMD_LAB
-  if (g.lab_clock) {
-    std::vector<unsigned long long> h(16 * (size_t)g.nchunks);
-    HIP_TRY(read_back(h.data(), lab_clk.p, sizeof(unsigned long long) * h.size()));
-    static const char *names[6] = {"hash + rank + barrier", "claim issue + scan + barrier", "regroup issue + claim answer", "prefetch issue + barrier",
-                                   "flush (LDS reads, store issue)", "wait for the next tile's keys"};
-    for (int wv = 0; wv < 2; ++wv) {
-      double sum[6] = {0, 0, 0, 0, 0, 0}, all = 0;
-      for (int c = 0; c < g.nchunks; ++c) for (int i = 0; i < 6; ++i) { sum[i] += (double)h[((size_t)c * 2 + wv) * 8 + i]; all += (double)h[((size_t)c * 2 + wv) * 8 + i]; }
-      fprintf(stderr, "jk_scatter1 phase clock, %s wave of every workgroup (%d chunks, %.0f cycles per chunk):\n", wv ? "last" : "first", g.nchunks, all / g.nchunks);
-      for (int i = 0; i < 6; ++i) fprintf(stderr, "  %-34s %5.1f %%\n", names[i], 100.0 * sum[i] / all);
-    }
-    g.lab_clock = nullptr;
-  }
-#endif
-#ifdef GDF_AMD_LAB
-  if (lab::knob_on("GDF_JK_TRACE")) {
-    std::vector<uint32_t> c1(nseg + 1);
-    HIP_TRY(read_back(c1.data(), spec.p, sizeof(uint32_t) * (nseg + 1)));
-    uint64_t sum = 0; uint32_t mx = 0, nz = 0;
-    for (uint32_t i = 0; i < nseg; ++i) { sum += c1[i]; mx = std::max(mx, c1[i]); nz += c1[i] != 0; }
-    fprintf(stderr, "level 1: nseg %u cap1 %u xs %d l6 %d chunks %d: fill sum %llu max %u nonzero %u flag %u\n", nseg, cap1, g.xs, (int)l6, g.nchunks,
-            (unsigned long long)sum, mx, nz, c1[nseg]);
-  }
-#endif
   if (defer && !app && g.b2 > 0) {
     // DEFERRED: the level-2 map and the fill cursors are made on the device, nothing is read back here; the overflow flags
     // of both levels are looked at once, with the work units (jk_make_units / probe_partitioned)
@@ -3837,11 +3734,11 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
     hipLaunchKernelGGL(jk_make_l2map, dim3(1), dim3(JK_BK_THREADS), map_lds, stream0(), (const uint32_t *)spec.as<uint32_t>(), nseg, cap1,
                        (uint32_t)JK_TILE2, seg_begin, seg_end, tile_prefix, ntiles_dev, 0u, 0u, g.rstart, g.rcap);
     HIP_CHECK_LAST();
-    const bool p6 = want_p6 && !pay && sc2_threads == 256;
+    const bool p6 = want_p6 && !pay;
     const bool hi_inside2 = placed && p6 && !narrow;          // (ten-byte tuples: the high words behind the six-byte stream, as at level 1)
     const size_t six2 = (6 * (size_t)size2 + 16 + 255) & ~(size_t)255;
     const size_t bytes2 = p6 ? (hi_inside2 ? six2 + sizeof(int32_t) * ((size_t)size2 + 2) : 6 * (size_t)size2 + 16) : sizeof(uint64_t) * size2;
-    if (placed) RMM_TRY(sb->w[1].alloc_placed(JK_ROLE_LEVEL2, bytes2, calibrate ? place_draws_now(JK_PLACE_DRAWS_L2) : JK_PLACE_DRAWS_L2));
+    if (placed) RMM_TRY(sb->w[1].alloc_placed(JK_ROLE_LEVEL2, bytes2, place_draws_now(JK_PLACE_DRAWS_L2)));
     else RMM_TRY(sb->w[1].alloc(bytes2));
     if (hi_inside2) sb->idx[1].borrow(sb->w[1].as<char>() + six2);
     else if (!narrow) RMM_TRY(sb->idx[1].alloc(sizeof(int32_t) * size2));
@@ -3856,13 +3753,13 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
     const uint32_t tile_bound = (uint32_t)((uint64_t)n / (uint64_t)JK_TILE2) + nseg + 1;
     // PLACEMENT TOURNAMENT of the level-2 buffer, as for level 1 above: every candidate is timed on a calibration run of the real
     // kernel over every fourth tile (all 2^15 write fronts open), the fill cursors are set back, the pool keeps the fastest
-    if (placed && calibrate) {
+    if (placed) {
       for (int round = 0; round <= JK_PLACE_DRAWS_L2 && sb->w[1].measure; ++round) {
         PlaceRound charge;
         Level2Map mc = m;
         mc.calib_step = 4;
         sb->w[1].clock_begin(stream0());
-        GDF_TRY(launch_scatter2(narrow, sc2_threads, tile_bound, g2, mc, sb->tuples(0), cursor.as<uint32_t>(), sb->tuples(1), p6, l6, pw));
+        GDF_TRY(launch_scatter2(narrow, tile_bound, g2, mc, sb->tuples(0), cursor.as<uint32_t>(), sb->tuples(1), p6, l6, pw));
         sb->w[1].clock_end(stream0());
         hipLaunchKernelGGL(jk_init_cursor, dim3(32), dim3(256), 0, stream0(), cursor.as<uint32_t>(), nfine, cap2, g.fstart);      // (+ the overflow flag)
         HIP_CHECK_LAST();
@@ -3871,7 +3768,7 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
       }
     }
     sb->w[1].clock_begin(stream0());
-    GDF_TRY(launch_scatter2(narrow, sc2_threads, tile_bound, g2, m, sb->tuples(0), cursor.as<uint32_t>(), sb->tuples(1), p6, l6, pw));
+    GDF_TRY(launch_scatter2(narrow, tile_bound, g2, m, sb->tuples(0), cursor.as<uint32_t>(), sb->tuples(1), p6, l6, pw));
     sb->w[1].clock_end(stream0());
     sb->p6 = p6;
     // no synchronisation: the map and the level-1 tuples stay allocated until probe_partitioned has read its state block
@@ -3929,7 +3826,7 @@ static gdf_error partition_side_spec(const KeyTable &t, const KeyPlan &plan, Par
     g2.dump = nfine * cap2;
     g2.spec_flag = cursor.as<uint32_t>() + nfine;
     Level2Map m{d_coarse.as<uint32_t>(), d_coarse.as<uint32_t>() + nseg, d_tiles.as<uint32_t>(), g.xs};
-    if (ntiles) GDF_TRY(launch_scatter2(narrow, sc2_threads, ntiles, g2, m, sb->tuples(0), cursor.as<uint32_t>(), sb->tuples(1), false, false, pw));
+    if (ntiles) GDF_TRY(launch_scatter2(narrow, ntiles, g2, m, sb->tuples(0), cursor.as<uint32_t>(), sb->tuples(1), false, false, pw));
     uint32_t flag = 0;
     if (!app) {
       cur.resize((size_t)nfine + 1);
@@ -4032,7 +3929,7 @@ static gdf_error run_probe(bool narrow, bool write, const char *name, size_t nun
 static gdf_error run_write_pass(bool narrow, bool plain, size_t nunits, size_t lds, ProbeArgs a, uint32_t max_build,
                                 const KeyTable &probe_t, const KeyTable &build_t) {
   if (!nunits) return GDF_SUCCESS;
-  if (!plain || lab::knob_on("GDF_JK_NO_FAST") || (!narrow && lab::knob_on("GDF_JK_NO_FAST_WIDE")))
+  if (!plain)
     return run_probe(narrow, true, "jk_probe_write", nunits, lds, a, probe_t, build_t);
   DevBuf todo;
   RMM_TRY(todo.alloc(sizeof(uint32_t) * nunits));
@@ -4102,7 +3999,6 @@ static gdf_error run_write_pass(bool narrow, bool plain, size_t nunits, size_t l
   HIP_CHECK_LAST();
   unsigned long long left = 0;
   HIP_TRY(read_back(&left, a.opt_state + 2, sizeof(left)));
-  if (LAB_BITS(a.dbg) & 256) fprintf(stderr, "jk_probe_fast: %llu of %zu units left to the general kernel\n", left, nunits);
   if (left) GDF_TRY(run_probe(narrow, true, "jk_probe_write_general", (size_t)left, lds, a, probe_t, build_t));
   HIP_TRY(hipStreamSynchronize(stream0()));      // `todo` goes out of scope
   return GDF_SUCCESS;
@@ -4135,7 +4031,7 @@ static gdf_error run_multi_pass(bool write, size_t nunits, size_t lds, const Pro
 static gdf_error run_count_pass(bool narrow, bool plain, size_t nunits, size_t lds, ProbeArgs a, uint32_t max_build,
                                 const KeyTable &probe_t, const KeyTable &build_t) {
   if (!nunits) return GDF_SUCCESS;
-  if (!plain || a.build_matched || lab::knob_on("GDF_JK_NO_FAST") || lab::knob_on("GDF_JK_NO_FAST_COUNT"))
+  if (!plain || a.build_matched)
     return run_probe(narrow, false, "jk_probe_count", nunits, lds, a, probe_t, build_t);
   DevBuf todo;
   RMM_TRY(todo.alloc(sizeof(uint32_t) * nunits));
@@ -4174,21 +4070,6 @@ static gdf_error run_count_pass(bool narrow, bool plain, size_t nunits, size_t l
 
 // The join proper.  probe_t / build_t already reflect the INNER-join swap.
 // On success *out_probe / *out_build own rmm allocations of *out_n int32 each.
-// host-side stage clock (GDF_JK_DBG & 512): where the time between the kernels goes
-struct StageClock {
-  bool on;
-  std::chrono::steady_clock::time_point t0, last;
-  explicit StageClock(bool enable) : on(enable), t0(std::chrono::steady_clock::now()), last(t0) {}
-  void mark(const char *what) {
-    if (!on) return;
-    (void)hipStreamSynchronize(stream0());
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "  [join] %-28s %8.3f ms (total %8.3f)\n", what, std::chrono::duration<double, std::milli>(now - last).count(),
-            std::chrono::duration<double, std::milli>(now - t0).count());
-    last = now;
-  }
-};
-
 // Third level: every one of the 2^fb partitions of `sb` (either layout) is split 2^b3-way by the next hash bits into a
 // new buffer in the speculative layout (partition f owns [f * cap3, (f + 1) * cap3), fill counters); jk_scatter2 does
 // the work, with the level-2 partitions as its segments.  *ok = false leaves `sb` untouched (a partition outgrew its
@@ -4199,8 +4080,7 @@ static gdf_error refine_side(const PartGeom &g, bool narrow, double dup, SideBuf
   const uint64_t nfine3 = (uint64_t)nseg << g.b3;
   const int64_t n = sb->joinable;
   if (n == 0) return GDF_SUCCESS;
-  const int threads = sb->pay[sb->final_buf].p ? 256 : level2_threads(narrow ? 1024 : 512);
-  const int64_t TILE = (int64_t)threads * (sb->pay[sb->final_buf].p ? JK_PAY_ITEMS : JK_SC_ITEMS);
+  const int64_t TILE = (int64_t)JK_SC2_THREADS * (sb->pay[sb->final_buf].p ? JK_PAY_ITEMS : JK_SC_ITEMS);
   const double mean = (double)n / (double)nfine3;
   const uint32_t cap3 = (uint32_t)(((uint64_t)(mean + 8.0 * std::sqrt(mean * (1.0 + dup)) + 64.0) + 7) / 8 * 8);
   const uint64_t size3 = nfine3 * cap3 + TILE;
@@ -4237,7 +4117,7 @@ static gdf_error refine_side(const PartGeom &g, bool narrow, double dup, SideBuf
   g3.spec_flag = flag.as<uint32_t>();
   g3.xs = 0;
   Level2Map m{d_seg.as<uint32_t>(), d_seg.as<uint32_t>() + nseg, d_tiles.as<uint32_t>(), 0};
-  if (ntiles) GDF_TRY(launch_scatter2(narrow, threads, ntiles, g3, m, sb->final(), cursor.as<uint32_t>(), Tuples{nw.as<uint64_t>(), nidx.as<int32_t>(), npay.as<uint64_t>()},
+  if (ntiles) GDF_TRY(launch_scatter2(narrow, ntiles, g3, m, sb->final(), cursor.as<uint32_t>(), Tuples{nw.as<uint64_t>(), nidx.as<int32_t>(), npay.as<uint64_t>()},
                                       false, false, sb->pay_words));
   uint32_t overflow = 0;
   HIP_TRY(read_back(cur.data(), cursor.p, sizeof(uint32_t) * nfine3));
@@ -4344,7 +4224,7 @@ static gdf_error prepare_build(const KeyTable &build_t, BuildSide *bs, bool no_l
 }
 
 static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &build_t, const BuildSide &bs, const KeyPlan &plan, SideBufs &P, JoinKind kind,
-                                   int32_t **out_probe, int32_t **out_build, int64_t *out_n, StageClock &clk, PayCarry *pc = nullptr);
+                                   int32_t **out_probe, int32_t **out_build, int64_t *out_n, PayCarry *pc = nullptr);
 
 // The probe side's skew sample (jk_sample_skew) needs nothing from the build pass: hash_join_core launches it BEFORE the build side is
 // partitioned, and its 4-byte answer is read when the probe side's turn comes -- no kernel + read-back round trip between the two sides.
@@ -4354,8 +4234,7 @@ struct SkewProbe {
   ReadTicket answer;          // the copy of the 4-byte answer is queued right behind the sample: whoever asks later waits for nothing
 };
 static bool skew_probe_wanted(const KeyTable &probe_t, const KeyPlan &plan, const PartGeom &g) {
-  return g.fb >= 10 && probe_t.nrows >= ((int64_t)1 << 24) && fast_key_width(probe_t, plan) && plan.mode == KM_RAW_INT &&
-         !lab::knob_on("GDF_JK_NO_SKEW_SAMPLE");
+  return g.fb >= 10 && probe_t.nrows >= ((int64_t)1 << 24) && fast_key_width(probe_t, plan) && plan.mode == KM_RAW_INT;
 }
 static gdf_error skew_probe_launch(const KeyTable &probe_t, const KeyPlan &plan, const PartGeom &g, SkewProbe *sp) {
   sp->words = ((size_t)1 << g.fb) + 1;
@@ -4373,7 +4252,7 @@ static gdf_error skew_probe_launch(const KeyTable &probe_t, const KeyPlan &plan,
 }
 
 static gdf_error probe_prepared(const KeyTable &probe_t, const KeyTable &build_t, const BuildSide &bs, JoinKind kind,
-                                int32_t **out_probe, int32_t **out_build, int64_t *out_n, StageClock &clk, PayCarry *pc = nullptr,
+                                int32_t **out_probe, int32_t **out_build, int64_t *out_n, PayCarry *pc = nullptr,
                                 SkewProbe *early_skew = nullptr) {
   // which probe rows travel (KeyPlan::kwindow): decided per probe call, on this call's COPY of the plan -- a prepared build side
   // serves INNER and LEFT probes alike, possibly from several threads at once
@@ -4406,7 +4285,7 @@ static gdf_error probe_prepared(const KeyTable &probe_t, const KeyTable &build_t
   }
   // the main path -- two-level speculative probe side, every build partition in LDS, no FULL-join marks -- keeps its
   // bookkeeping on the device (see jk_make_units)
-  const bool defer = g.b2 > 0 && g.b3 == 0 && kind != JOIN_FULL && B.d_cnt.p != nullptr && !lab::knob_on("GDF_JK_NO_DEFER");
+  const bool defer = g.b2 > 0 && g.b3 == 0 && kind != JOIN_FULL && B.d_cnt.p != nullptr;
   // the probe relation's payload column(s) ride along (PayCarry) when the join runs on NARROW tuples with exact keys from
   // one FAST, unmasked key column; everything else leaves pc->carried false and the caller gathers as before
   PaySrc pay_src{};
@@ -4473,19 +4352,18 @@ static gdf_error probe_prepared(const KeyTable &probe_t, const KeyTable &build_t
     GDF_TRY(refine_side(g, narrow, std::max(1.0, (double)probe_t.nrows / std::max<uint32_t>(B.joinable, 1)), &P, &ok));
     if (!ok) return GDF_AMD_RETRY_WITHOUT_LEVEL3;     // skewed probe keys: the caller repeats with a 2^fb-partition build side
   }
-  clk.mark("partition probe side");
-  gdf_error e = probe_partitioned(probe_t, build_t, bs, plan, P, kind, out_probe, out_build, out_n, clk, pc_eff);
+  gdf_error e = probe_partitioned(probe_t, build_t, bs, plan, P, kind, out_probe, out_build, out_n, pc_eff);
   if (e != GDF_AMD_RETRY_EXACT_PROBE) return e;
   // a deferred speculative probe side turned out to have overflowed (skewed keys): the exact layout, host bookkeeping
   SideBufs Q;
   KeyPlan probe_plan = plan;
   GDF_TRY(partition_side(probe_t, probe_plan, g, &Q, false, pay, pmode, false, want_p6_exact));
-  return probe_partitioned(probe_t, build_t, bs, plan, Q, kind, out_probe, out_build, out_n, clk, pc_eff);
+  return probe_partitioned(probe_t, build_t, bs, plan, Q, kind, out_probe, out_build, out_n, pc_eff);
 }
 
 // the part of a join after both relations are partitioned: work units, optimistic single pass or count + write, tails
 static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &build_t, const BuildSide &bs, const KeyPlan &plan, SideBufs &P, JoinKind kind,
-                                   int32_t **out_probe, int32_t **out_build, int64_t *out_n, StageClock &clk, PayCarry *pc) {
+                                   int32_t **out_probe, int32_t **out_build, int64_t *out_n, PayCarry *pc) {
   const PartGeom &g = bs.g;
   const SideBufs &B = bs.B;
   const uint32_t nfine = 1u << (g.fb + g.b3);
@@ -4620,7 +4498,6 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
   a.keep_unmatched_probe = keep_probe ? 1 : 0;
   a.verify = plan.verify;
   a.build_matched = d_matched.as<uint8_t>();
-  a.dbg = (int)lab::knob_int("GDF_JK_DBG", 0);
   a.kbias = plan.kmin;
   if (P.p6) {                       // six-byte probe tuples: the kernels hash and compare hash remainders (ProbeArgs::p6_fb)
     a.p6_fb = g.fb;
@@ -4635,7 +4512,6 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
   // The lean write kernel would give up on nearly every unit after four cuckoo attempts (5.7 of 31 ms on a join whose
   // build keys all occur four times, profiles/r2_b_bench_shapes.jsonl) -- such joins go to the general kernel directly.
   bool dup_heavy = false;
-  clk.mark("units + argument setup");
   // ---- optimistic single pass ----
   // A foreign-key -> primary-key join whose every probe row finds its key emits exactly one pair per
   // probe tuple.  Then unit u's output is its probe_count slots at the prefix sum of the probe counts
@@ -4652,23 +4528,19 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
     sa.sample_n = (uint32_t)NSAMPLE;
     sa.nunits_dev = d_bk.as<unsigned long long>();
     sa.opt_state = d_bk.as<unsigned long long>() + 4;
-    if (!(LAB_BITS(a.dbg) & 16)) GDF_TRY(run_probe(narrow, false, "jk_probe_sample", NSAMPLE, probe_lds, sa, probe_t, build_t));
+    GDF_TRY(run_probe(narrow, false, "jk_probe_sample", NSAMPLE, probe_lds, sa, probe_t, build_t));
     HIP_TRY(read_back(bk, d_bk.p, sizeof(bk)));
     P.w[0].reset();                        // level-1 tuples and the segment map: everything that read them has run
     P.idx[0].reset();
     P.d_map.reset();
-#ifdef GDF_AMD_LAB
-    if (lab::knob_on("GDF_JK_TRACE")) fprintf(stderr, "deferred probe side: overflow flags %llu (1 = level 2, 2 = level 1), units %llu, tuples %llu\n", bk[3], bk[0], bk[2]);
-#endif
     if (bk[3]) return GDF_AMD_RETRY_EXACT_PROBE;
     nunits = (size_t)bk[0];
     cap_pairs = bk[1];
     P.joinable = (uint32_t)bk[2];
     dup_heavy = bk[7] * 4 >= NSAMPLE;
-    try_optimistic = nunits && !(LAB_BITS(a.dbg) & 16) && bk[4] == bk[5];
+    try_optimistic = nunits && bk[4] == bk[5];
     sample_hit = bk[5] ? (double)bk[4] / (double)bk[5] : 1.0;
-    clk.mark("sample count");
-  } else if (nunits && oversize.empty() && kind != JOIN_FULL && !(LAB_BITS(a.dbg) & 16)) {
+  } else if (nunits && oversize.empty() && kind != JOIN_FULL) {
     const size_t nsample = std::min<size_t>(nunits, NSAMPLE);
     std::vector<Unit> sample(nsample);
     uint64_t sample_tuples = 0;
@@ -4696,7 +4568,6 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
     unsigned long long sstate[4] = {0, 0, 0, 0};
     HIP_TRY(read_back(sstate, d_sstate.p, sizeof(sstate)));
     dup_heavy = sstate[3] * 4 >= nsample;
-    clk.mark("sample count");
     uint64_t sample_pairs = 0;
     for (uint64_t c : scount) sample_pairs += c;
     try_optimistic = sample_pairs == sample_tuples;
@@ -4710,8 +4581,8 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
   // 16 B per pair), from a third on by moving only the pairs behind the final size into the holes in front of it (jk_fill_holes:
   // h (1 - h) of the slots; the columns keep their allocation of one slot per probe tuple).  A unit that runs out of slots
   // (a build key present more than once after all) sends the call to count + write.
-  const bool try_sparse = !try_optimistic && d_off.p && nunits && oversize.empty() && kind == JOIN_INNER && !dup_heavy && !(LAB_BITS(a.dbg) & 16) &&
-                          sample_hit <= lab::knob_float("GDF_JK_SPARSE_MAX", 1.0) && !lab::path_on("GDF_JK_NO_SPARSE_OPT");
+  const bool try_sparse = !try_optimistic && d_off.p && nunits && oversize.empty() && kind == JOIN_INNER && !dup_heavy &&
+                          sample_hit <= 1.0 && !lab::path_on("GDF_JK_NO_SPARSE_OPT");
   if (try_optimistic || try_sparse) {
     DevBuf d_state, d_upairs;
     if (deferred && P.zero) d_state.borrow(P.zero + 12);
@@ -4724,7 +4595,7 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
     if (total >= (uint64_t)INT_MAX) return GDF_COLUMN_SIZE_TOO_BIG;
     // the two index columns of a large dense join are PLACED blocks too (the probe kernel's 2 x 4 GB of writes have their fast and
     // slow placements like the regroup passes'): tournament below; the caller gets the winners and frees them through rmmFree as ever
-    const bool place_out = try_optimistic && nunits >= 64 && !lab::knob_on("GDF_JK_NO_CALIBRATE");
+    const bool place_out = try_optimistic && nunits >= 64;
     const size_t out_bytes = sizeof(int32_t) * (size_t)(total ? total : 1);
     DevBuf op, ob;
     if (place_out) {
@@ -4767,13 +4638,11 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
       oa.out_probe = op.as<int32_t>();
       oa.out_build = ob.as<int32_t>();
     }
-    clk.mark("output allocation");
     P.w[P.final_buf].clock_begin(stream0());      // (a placed level-2 block: the probe kernel reads it)
     GDF_TRY(run_write_pass(narrow, plain && !dup_heavy, nunits, probe_lds, oa, max_build, probe_t, build_t));
     P.w[P.final_buf].clock_end(stream0());
     unsigned long long st[2] = {0, 0};
     HIP_TRY(read_back(st, d_state.p, sizeof(st)));
-    clk.mark("write pass");
     if (st[1] == 0 && st[0] == cap_pairs) {       // dense: every slot of every unit was written
       if (probe_tail) {
         GDF_LAUNCH("jk_emit_unjoinable", jk_emit_unjoinable, dim3(small_grid(probe_t.nrows)), dim3(256), 0, stream0(), probe_t, plan,
@@ -4788,7 +4657,7 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
       commit_pay();
       return GDF_SUCCESS;
     }
-    if (try_sparse && st[1] == 0 && st[0] * 3 >= cap_pairs && !lab::knob_on("GDF_JK_NO_HOLE_FILL")) {
+    if (try_sparse && st[1] == 0 && st[0] * 3 >= cap_pairs) {
       // most slots are taken: move only the pairs behind the final size into the holes in front of it (jk_fill_holes)
       const uint64_t pairs = st[0];
       DevBuf d_holes, d_tails;
@@ -4805,7 +4674,6 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
                  (const uint64_t *)d_tails.as<uint64_t>(), op.as<int32_t>(), ob.as<int32_t>(), pm);
       HIP_CHECK_LAST();
       HIP_TRY(hipStreamSynchronize(stream0()));
-      clk.mark("hole filling");
       *out_n = (int64_t)pairs;
       *out_probe = (int32_t *)op.release();        // (allocated for cap_pairs slots, `pairs` of them in use)
       *out_build = (int32_t *)ob.release();
@@ -4831,7 +4699,6 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
                  fb.as<int32_t>(), pm);
       HIP_CHECK_LAST();
       HIP_TRY(hipStreamSynchronize(stream0()));
-      clk.mark("compaction");
       *out_probe = (int32_t *)fp.release();
       *out_build = (int32_t *)fb.release();
       for (int c = 0; c < ncc; ++c) { cc[c].buf.reset(); cc[c].buf.p = dense_pay[c].release(); }
@@ -4964,7 +4831,6 @@ static gdf_error probe_partitioned(const KeyTable &probe_t, const KeyTable &buil
 
 static gdf_error hash_join_core(const KeyTable &probe_t, const KeyTable &build_t, JoinKind kind, int32_t **out_probe,
                                 int32_t **out_build, int64_t *out_n, PayCarry *pc = nullptr) {
-  StageClock clk((lab::knob_int("GDF_JK_DBG", 0) & 512) != 0);
   BuildSide bs;
   PaySrc bsrc{};
   const bool bcarry = pc && pc->mode >= 0 && pc->bmode && kind == JOIN_INNER && !lab::path_on("GDF_JK_NO_CARRY");
@@ -4977,13 +4843,12 @@ static gdf_error hash_join_core(const KeyTable &probe_t, const KeyTable &build_t
   }
   // (the build side's last launches are still queued when this returns: the probe side's first ones follow without a host round trip)
   GDF_TRY(prepare_build(build_t, &bs, false, bcarry ? &bsrc : nullptr, bcarry ? pc->bmode : 0, true));
-  clk.mark("partition build side");
-  gdf_error e = probe_prepared(probe_t, build_t, bs, kind, out_probe, out_build, out_n, clk, pc, &early_skew);
+  gdf_error e = probe_prepared(probe_t, build_t, bs, kind, out_probe, out_build, out_n, pc, &early_skew);
   bs.B.settle();
   if (e != GDF_AMD_RETRY_WITHOUT_LEVEL3) return e;
   BuildSide plain;
   GDF_TRY(prepare_build(build_t, &plain, true, bcarry ? &bsrc : nullptr, bcarry ? pc->bmode : 0));
-  return probe_prepared(probe_t, build_t, plain, kind, out_probe, out_build, out_n, clk, pc, &early_skew);
+  return probe_prepared(probe_t, build_t, plain, kind, out_probe, out_build, out_n, pc, &early_skew);
 }
 
 // FULL join with an empty side (joining.cu:214-280 trivial_full_join): every row of
@@ -5401,10 +5266,8 @@ gdf_error debug_partition(gdf_column *col, int fb, uint64_t *out_key, int32_t *o
   GDF_TRY(make_key_table(cols, 1, &t));
   KeyPlan plan = plan_keys(t);
   PartGeom g{};
-  g.dbg = (int)lab::knob_int("GDF_JK_SDBG", 0);
   g.fb = fb;
   g.b1 = fb <= 8 ? fb : (fb + 1) / 2;
-  if (lab::knob_on("GDF_JK_B1") && fb > 8) { const int b1 = (int)lab::knob_int("GDF_JK_B1", 0); if (b1 >= fb - 8 && b1 <= 8) g.b1 = b1; }   // experiment switch
   g.b2 = fb - g.b1;
   SideBufs sb;
   GDF_TRY(partition_side(t, plan, g, &sb, !plan.narrow && plan.mode == KM_RAW_INT && t.col[0].width == 8));
@@ -5483,14 +5346,13 @@ static gdf_error build_probe(PreparedBuild *pb, int left_join, gdf_column **prob
   GDF_TRY(make_key_table(probe_cols, num_cols, &pt));
   gdf_column_view(probe_indices, nullptr, nullptr, 0, N_GDF_TYPES);
   gdf_column_view(build_indices, nullptr, nullptr, 0, N_GDF_TYPES);
-  StageClock clk((lab::knob_int("GDF_JK_DBG", 0) & 512) != 0);
   int32_t *o_probe = nullptr, *o_build = nullptr;
   int64_t n = 0;
-  gdf_error e = probe_prepared(pt, pb->table, pb->side, kind, &o_probe, &o_build, &n, clk);
+  gdf_error e = probe_prepared(pt, pb->table, pb->side, kind, &o_probe, &o_build, &n);
   if (e == GDF_AMD_RETRY_WITHOUT_LEVEL3) {           // skewed probe keys against a three-level build side: rebuild it plainly, once
     BuildSide plain;
     GDF_TRY(prepare_build(pb->table, &plain, true));
-    e = probe_prepared(pt, pb->table, plain, kind, &o_probe, &o_build, &n, clk);
+    e = probe_prepared(pt, pb->table, plain, kind, &o_probe, &o_build, &n);
   }
   GDF_TRY(e);
   if (n == 0) return GDF_SUCCESS;
@@ -5522,7 +5384,7 @@ static gdf_error accum_begin(PreparedBuild *pb, size_t expected_rows, ProbeAccum
   uint32_t largest_build = 0;
   for (uint32_t c : pb->side.B.fine_cnt) largest_build = std::max(largest_build, c);
   if (!pb->partitioned || plan.verify || !plan.narrow || g.b2 == 0 || g.b3 != 0 || largest_build > (uint32_t)JK_MAX_BUILD ||
-      (!pb->fj && (expected_rows < ((size_t)1 << 22) || lab::knob_on("GDF_JK_NO_ACCUM"))))
+      (!pb->fj && expected_rows < ((size_t)1 << 22)))
     return GDF_UNSUPPORTED_METHOD;
   std::unique_ptr<ProbeAccum> a(new ProbeAccum());
   a->pb = pb;
@@ -5567,7 +5429,7 @@ static gdf_error accum_finish(ProbeAccum *a, gdf_column *probe_indices, gdf_colu
   // A fused receiver's probe side goes the DEFERRED way of the single-GPU main path (round 5): its fill cursors and their overflow flag
   // are what jk_make_units reads -- units, output offsets and the sample are made on the device and ONE state block comes back, instead of
   // the flag, then 2^15 cursors, then a unit list walked and uploaded by the host (0.25 ms of idle GPU in front of the probe kernel)
-  if (a->pb->fj && a->pb->side.B.d_cnt.p && a->pb->side.B.d_begin.p && !lab::knob_on("GDF_JK_NO_DEFER")) {
+  if (a->pb->fj && a->pb->side.B.d_cnt.p && a->pb->side.B.d_begin.p) {
     a->P.deferred = true;
     a->P.speculative = true;
     a->P.cap2 = a->app.cap2;
@@ -5579,10 +5441,9 @@ static gdf_error accum_finish(ProbeAccum *a, gdf_column *probe_indices, gdf_colu
     all.nrows = a->app.rows;
     for (int c = 0; c < all.ncols; ++c) { all.col[c].data = nullptr; all.col[c].valid = nullptr; }
     all.any_valid = 0;
-    StageClock clk(false);
     int32_t *o_probe = nullptr, *o_build = nullptr;
     int64_t n = 0;
-    const gdf_error e = probe_partitioned(all, a->pb->table, a->pb->side, a->pb->side.plan, a->P, JOIN_INNER, &o_probe, &o_build, &n, clk);
+    const gdf_error e = probe_partitioned(all, a->pb->table, a->pb->side, a->pb->side.plan, a->P, JOIN_INNER, &o_probe, &o_build, &n);
     if (e == GDF_AMD_RETRY_EXACT_PROBE) return GDF_UNSUPPORTED_METHOD;          // a fine partition outgrew its room (the flag, as below)
     GDF_TRY(e);
     if (n == 0) return GDF_SUCCESS;
@@ -5601,10 +5462,9 @@ static gdf_error accum_finish(ProbeAccum *a, gdf_column *probe_indices, gdf_colu
   all.nrows = a->app.rows;
   for (int c = 0; c < all.ncols; ++c) { all.col[c].data = nullptr; all.col[c].valid = nullptr; }
   all.any_valid = 0;
-  StageClock clk(false);
   int32_t *o_probe = nullptr, *o_build = nullptr;
   int64_t n = 0;
-  GDF_TRY(probe_partitioned(all, a->pb->table, a->pb->side, a->pb->side.plan, a->P, JOIN_INNER, &o_probe, &o_build, &n, clk));
+  GDF_TRY(probe_partitioned(all, a->pb->table, a->pb->side, a->pb->side.plan, a->P, JOIN_INNER, &o_probe, &o_build, &n));
   if (n == 0) return GDF_SUCCESS;
   gdf_column_view(probe_indices, o_probe, nullptr, (gdf_size_type)n, GDF_INT32);
   gdf_column_view(build_indices, o_build, nullptr, (gdf_size_type)n, GDF_INT32);
@@ -5911,8 +5771,7 @@ static gdf_error fj_level2(const uint32_t *keys, const uint32_t *fill, uint32_t 
   const uint32_t nfine = 1u << g.fb;
   // (world x coarse partitions = 1024 leaves 8 bits to level 2: 256 bins per 4096-tuple tile, (tile, bin) runs of 16 tuples.  8192-tuple
   // tiles -- 512 threads, runs of 32 as on the single-GPU path -- were slower: 4.15 vs 3.52 ms per 1e9 keys, profiles/r3_o_fused_level2.txt)
-  const int sc2_threads = 256;
-  const int64_t TILE2 = (int64_t)sc2_threads * JK_SC_ITEMS;
+  const int64_t TILE2 = (int64_t)JK_SC2_THREADS * JK_SC_ITEMS;
   keep->emplace_back();
   DevBuf &d_map = keep->back();
   RMM_TRY(d_map.alloc(sizeof(uint32_t) * (3 * (size_t)nseg + 2)));
@@ -5935,7 +5794,7 @@ static gdf_error fj_level2(const uint32_t *keys, const uint32_t *fill, uint32_t 
   m.keys32 = keys;
   m.calib_step = calib_step;          // (> 1: a calibration run of the level-2 buffer's placement tournament, fj_probe_add)
   const uint32_t tile_bound = (uint32_t)(((uint64_t)nseg * cap) / (uint64_t)TILE2) + nseg + 1;
-  GDF_TRY(launch_scatter2(true, sc2_threads, tile_bound, g2, m, Tuples{nullptr, nullptr, nullptr}, cursor, out, p6));
+  GDF_TRY(launch_scatter2(true, tile_bound, g2, m, Tuples{nullptr, nullptr, nullptr}, cursor, out, p6));
   return GDF_SUCCESS;
 }
 
@@ -6037,7 +5896,7 @@ static gdf_error fj_probe_add(ProbeAccum *a, const uint32_t *recv_keys, const ui
     // every fourth tile of this first slice, the cursors are set back, the pool keeps the fastest
     const size_t bytes2 = a->P.p6 ? 6 * size2 + 16 : sizeof(uint64_t) * size2;
     RMM_TRY(a->P.w[1].alloc_placed(JK_ROLE_FUSED_LEVEL2, bytes2, JK_PLACE_DRAWS_L2));
-    for (int round = 0; round <= JK_PLACE_DRAWS_L2 && a->P.w[1].measure && !lab::knob_on("GDF_JK_NO_CALIBRATE"); ++round) {
+    for (int round = 0; round <= JK_PLACE_DRAWS_L2 && a->P.w[1].measure; ++round) {
       a->P.w[1].clock_begin(stream0());
       GDF_TRY(fj_level2(recv_keys, recv_fill, nseg, cap, g, a->app.cap2, (int32_t)position_base, a->app.cursor.as<uint32_t>(), a->P.tuples(1), &a->keep,
                         a->P.p6, 4));

@@ -184,8 +184,8 @@ __device__ __forceinline__ bool lb_read(const unsigned long long *slot, ACC &v) 
 
 template <class ACC, class ELEM, bool ROUNDS = false>
 __global__ __launch_bounds__(LB_THREADS) void scan_lookback(const ELEM *in, ELEM *out, size_t n, int inclusive,
-                                                            unsigned long long *state, uint32_t *ticket, uint32_t ntiles, int dbg) {
-  // dbg & 8: ROUNDS mode (round 6).  No chain and no walk: workgroup b takes tiles b, b + G, b + 2G, ... (G = gridDim.x, all resident),
+                                                            unsigned long long *state, uint32_t *ticket, uint32_t ntiles, int mode_bits) {
+  // mode_bits & 8: ROUNDS mode (round 6).  No chain and no walk: workgroup b takes tiles b, b + G, b + 2G, ... (G = gridDim.x, all resident),
   // round r is the G tiles r G ... r G + G - 1.  A workgroup publishes its tile's aggregate in slot [r & 3][b] (words tagged r + 1) one
   // pipeline step before it needs the others', then reads ALL G slots of the round in one batch of loads: the aggregates of the
   // workgroups before it are its tile's offset inside the round, their total advances its own running carry -- every workgroup adds
@@ -208,12 +208,12 @@ __global__ __launch_bounds__(LB_THREADS) void scan_lookback(const ELEM *in, ELEM
   __shared__ uint32_t s_first[NWAVES];
   const int wave = threadIdx.x / WAVE, lane = lane_id();
 
-  // dbg & 4: SPINE mode.  Workgroup 0 does nothing but turn tile aggregates into exclusive prefixes, in tile order: every
+  // mode_bits & 4: SPINE mode.  Workgroup 0 does nothing but turn tile aggregates into exclusive prefixes, in tile order: every
   // round it reads the next 1024 aggregates (four per thread, all loads in flight together), takes the leading run that
   // is already published, scans it and publishes the prefixes.  A worker then polls ONE word -- its own prefix -- instead
   // of walking back over hundreds of predecessors, each round of which is a cross-XCD round trip.  The spine consumes up
   // to 1024 tiles per round trip (~2.5 us): several times the ~80 tiles per us the data path needs.
-  if (!ROUNDS && (dbg & 4) && blockIdx.x == 0) {
+  if (!ROUNDS && (mode_bits & 4) && blockIdx.x == 0) {
     constexpr int PT = 4;
     ACC carry = 0;
     uint32_t base = 0;
@@ -445,7 +445,7 @@ __global__ __launch_bounds__(LB_THREADS) void scan_lookback(const ELEM *in, ELEM
   // prefix 0); both words of a predecessor are requested together -- one round trip, not two
   auto resolve = [&](const Scanned &sc) -> ACC {
     if constexpr (ROUNDS) return resolve_rounds(sc);
-    if (dbg & 4) {                  // spine mode: the tile's exclusive prefix arrives in its own slot
+    if (mode_bits & 4) {            // spine mode: the tile's exclusive prefix arrives in its own slot
       block_sync();                 // s_excl's previous readers are done
       if (threadIdx.x == 0) {
         ACC e = 0;
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(LB_THREADS) void scan_lookback(const ELEM *in, ELEM
     }
     ACC exclusive = 0;
     long long nearest = (long long)sc.tile - 1;
-    for (; !(LAB_BITS(dbg) & 2);) {           // dbg & 2 (experiment): no look-back, wrong prefixes
+    for (;;) {
       const long long p = nearest - (long long)threadIdx.x;
       int st = 2;
       ACC val = 0;
@@ -591,32 +591,31 @@ template <class ACC, class ELEM, bool ROUNDS>
 static gdf_error device_scan_lookback_impl(const ELEM *in, ELEM *out, size_t n, bool inclusive, long long mode) {
   constexpr int NW = sizeof(ACC) / 4;
   const size_t ntiles = (n + LB_TILE - 1) / LB_TILE;
-  const int dbg = (int)lab::knob_int("GDF_SCAN_DBG", 0) | (mode == 2 ? 4 : 0) | (ROUNDS ? 8 : 0);      // 2: spine mode, 3: rounds
+  const int mode_bits = (mode == 2 ? 4 : 0) | (ROUNDS ? 8 : 0);      // 2: spine mode, 3: rounds
   DevBuf st;
   const size_t state_bytes = sizeof(unsigned long long) * (ROUNDS ? (size_t)4 * 4 * LB_THREADS * NW : ntiles * 2 * NW);
   RMM_TRY(st.alloc(state_bytes + 2 * sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(st.p, 0, state_bytes + 2 * sizeof(unsigned long long), stream0()));
   uint32_t *ticket = reinterpret_cast<uint32_t *>(st.as<unsigned char>() + state_bytes);
   // persistent workgroups, each takes tiles from the ticket counter until they run out: a few per CU (every one keeps two
-  // tiles in flight).  With dbg & 1 every workgroup handles exactly the tile of its blockIdx.
-  const int per_cu_env = (int)lab::knob_int("GDF_SCAN_WGS_PER_CU", 0);
+  // tiles in flight).
   int fit = 1;
   HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, (const void *)scan_lookback<ACC, ELEM, ROUNDS>, LB_THREADS, 0));
   if (fit < 1) fit = 1;
-  int per_cu = per_cu_env > 0 ? per_cu_env : fit;
-  size_t grid = (dbg & 1) ? ntiles : (size_t)NUM_CU * (size_t)per_cu;
+  size_t grid = (size_t)NUM_CU * (size_t)fit;
   // rounds: every workgroup must be resident (they wait for one another) and the poll reads <= 4 * LB_THREADS slots
-  if (ROUNDS) grid = (size_t)device_cu_count() * (size_t)std::max(1, std::min(std::min(per_cu_env > 0 ? per_cu_env : 4, fit), 4));
+  if (ROUNDS) grid = (size_t)device_cu_count() * (size_t)std::min(fit, 4);
   if (ROUNDS && grid > (size_t)4 * LB_THREADS) grid = (size_t)4 * LB_THREADS;        // (the slots one poll covers)
-  if (grid > ntiles + ((dbg & 4) ? 1 : 0)) grid = ntiles + ((dbg & 4) ? 1 : 0);      // spine mode: workgroup 0 takes no tiles
-  if ((dbg & 4) && grid < 2) grid = 2;
+  const size_t spine = (mode_bits & 4) ? 1 : 0;                    // spine mode: workgroup 0 takes no tiles
+  if (grid > ntiles + spine) grid = ntiles + spine;
+  if (spine && grid < 2) grid = 2;
   if (ROUNDS && lab::path_on("GDF_SCAN_FORCE_BAIL")) {      // test switch: the kernel leaves at once, the caller takes the three launches
     const uint32_t one = 1;
     HIP_TRY(hipMemcpyAsync(ticket + 1, &one, sizeof(one), hipMemcpyHostToDevice, stream0()));
     HIP_TRY(hipStreamSynchronize(stream0()));
   }
   GDF_LAUNCH(ROUNDS ? "scan_rounds" : "scan_lookback", (scan_lookback<ACC, ELEM, ROUNDS>), dim3((unsigned)grid), dim3(LB_THREADS), 0, stream0(), in, out, n,
-             inclusive ? 1 : 0, st.as<unsigned long long>(), ticket, (uint32_t)ntiles, dbg);
+             inclusive ? 1 : 0, st.as<unsigned long long>(), ticket, (uint32_t)ntiles, mode_bits);
   HIP_CHECK_LAST();
   if (ROUNDS) {                               // a grid that was not resident bailed out -- the caller takes the three launches
     uint32_t bailed = 0;
@@ -791,11 +790,10 @@ static gdf_error device_scan_coalesced(const ELEM *in, ELEM *out, size_t n, bool
   return GDF_SUCCESS;
 }
 
-// GDF_SCAN_SEG_MB=<n> scans the input in segments of n MiB (reduce -> spine -> apply per segment) so that the apply
-// pass re-reads what the reduce pass has just pulled through the 256 MiB Infinity Cache.  Measured on 1e8 int64:
-// scan_apply drops from 0.33 to 0.27 ms at 128 MiB segments, but the smaller grids slow scan_reduce (0.17 -> 0.24 ms)
-// and the extra launches add gaps -- 0.64 ms against 0.55 ms for the whole array in one go.  So the default is one
-// segment; the switch stays for larger inputs / other parts.
+// The whole array in one go.  Scanning in segments (reduce -> spine -> apply per 128 MiB segment, so that the apply pass
+// re-reads what the reduce pass has just pulled through the 256 MiB Infinity Cache) lost on 1e8 int64: scan_apply drops
+// from 0.33 to 0.27 ms, but the smaller grids slow scan_reduce (0.17 -> 0.24 ms) and the extra launches add gaps -- 0.64 ms
+// against 0.55 ms.
 template <class ACC, class ELEM>
 gdf_error device_scan(const ELEM *in, ELEM *out, size_t n, bool inclusive) {
   if (n == 0) return GDF_SUCCESS;
@@ -820,25 +818,19 @@ gdf_error device_scan(const ELEM *in, ELEM *out, size_t n, bool inclusive) {
   }
   constexpr int ITEMS = 16 / sizeof(ELEM) >= 4 ? 8 : 4;
   constexpr size_t TILE = (size_t)SCAN_THREADS * ITEMS;
-  const size_t seg_bytes = (size_t)lab::knob_int("GDF_SCAN_SEG_MB", 0) << 20;
-  size_t seg = seg_bytes ? seg_bytes / sizeof(ELEM) / TILE * TILE : (n + TILE - 1) / TILE * TILE;
-  if (seg < TILE) seg = TILE;
   DevBuf sums, running;
   RMM_TRY(sums.alloc(sizeof(ACC) * SCAN_MAX_CHUNKS));
   RMM_TRY(running.alloc(sizeof(ACC)));
   HIP_TRY(hipMemsetAsync(running.p, 0, sizeof(ACC), stream0()));
-  for (size_t s0 = 0; s0 < n; s0 += seg) {
-    const size_t m = n - s0 < seg ? n - s0 : seg;
-    // chunks are whole tiles so that thread-contiguous loads stay aligned
-    const size_t tiles = (m + TILE - 1) / TILE;
-    const size_t tiles_per_chunk = (tiles + SCAN_MAX_CHUNKS - 1) / SCAN_MAX_CHUNKS;
-    const size_t chunk = tiles_per_chunk * TILE;
-    const int nchunks = (int)((m + chunk - 1) / chunk);
-    GDF_LAUNCH("scan_reduce", (scan_reduce<ACC, ELEM, ITEMS>), dim3(nchunks), dim3(SCAN_THREADS), 0, stream0(), in + s0, sums.as<ACC>(), m, chunk);
-    hipLaunchKernelGGL((scan_spine<ACC>), dim3(1), dim3(SCAN_THREADS), 0, stream0(), sums.as<ACC>(), nchunks, running.as<ACC>());
-    GDF_LAUNCH("scan_apply", (scan_apply<ACC, ELEM, ITEMS>), dim3(nchunks), dim3(SCAN_THREADS), 0, stream0(), in + s0, out + s0, sums.as<ACC>(), m, chunk,
-               inclusive ? 1 : 0);
-  }
+  // chunks are whole tiles so that thread-contiguous loads stay aligned
+  const size_t tiles = (n + TILE - 1) / TILE;
+  const size_t tiles_per_chunk = (tiles + SCAN_MAX_CHUNKS - 1) / SCAN_MAX_CHUNKS;
+  const size_t chunk = tiles_per_chunk * TILE;
+  const int nchunks = (int)((n + chunk - 1) / chunk);
+  GDF_LAUNCH("scan_reduce", (scan_reduce<ACC, ELEM, ITEMS>), dim3(nchunks), dim3(SCAN_THREADS), 0, stream0(), in, sums.as<ACC>(), n, chunk);
+  hipLaunchKernelGGL((scan_spine<ACC>), dim3(1), dim3(SCAN_THREADS), 0, stream0(), sums.as<ACC>(), nchunks, running.as<ACC>());
+  GDF_LAUNCH("scan_apply", (scan_apply<ACC, ELEM, ITEMS>), dim3(nchunks), dim3(SCAN_THREADS), 0, stream0(), in, out, sums.as<ACC>(), n, chunk,
+             inclusive ? 1 : 0);
   HIP_CHECK_LAST();
   HIP_TRY(hipStreamSynchronize(stream0()));   // scratch is released on return
   return GDF_SUCCESS;

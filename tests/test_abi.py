@@ -294,10 +294,10 @@ def test_host_side_argument_errors_need_no_gpu(libs):
 
 
 def test_shipped_library_reads_no_environment(libs, hook):
-    """csrc/lab.h: the shipped libgdf.so / librmm.so import no getenv at all -- a stray GDF_* variable in a caller's
-    environment cannot change which algorithm runs -- and (round 6) libgdf.so exports no path switch either:
-    gdf_amd_debug_force lives in libgdf_testhook.so (csrc/testhook.cpp, test infrastructure), libgdf.so only has a WEAK reference
-    to that library's lookup, null in every process that did not load it first."""
+    """csrc/lab.h: libgdf.so / librmm.so import no getenv at all, and no source under csrc/ even contains the word -- a stray GDF_*
+    variable in a caller's environment cannot change which algorithm runs -- and (round 6) libgdf.so exports no
+    path switch either: gdf_amd_debug_force lives in libgdf_testhook.so (csrc/testhook.cpp, test infrastructure), libgdf.so only has
+    a WEAK reference to that library's lookup, null in every process that did not load it first."""
     for name in ("libgdf.so", "librmm.so"):
         und = subprocess.check_output(["nm", "-D", "--undefined-only", os.path.join(LIBDIR, name)]).decode()
         assert "getenv" not in und, name
@@ -310,9 +310,12 @@ def test_shipped_library_reads_no_environment(libs, hook):
     assert hook.gdf_amd_debug_force(b"GDF_JK_NO_SPEC", None) == 0
     assert hook.gdf_amd_testhook_forced(b"GDF_JK_NO_SPEC") is None
     assert hook.gdf_amd_debug_force(None, None) != 0
-    lab = os.path.join(LIBDIR, "lab", "libgdf.so")
-    if os.path.exists(lab):        # the LAB build (experiment knobs) is the one that reads the environment
-        assert "getenv" in subprocess.check_output(["nm", "-D", "--undefined-only", lab]).decode()
+    csrc = os.path.join(os.path.dirname(LIBDIR), "csrc")
+    sources = sorted(os.listdir(csrc))
+    assert "lab.h" in sources and "join.hip" in sources
+    for name in sources:
+        with open(os.path.join(csrc, name), errors="replace") as f:
+            assert "getenv" not in f.read(), name
 
 
 def test_no_exception_crosses_the_c_boundary(libs, hook):

@@ -46,8 +46,8 @@ def test_build_id_tracks_the_kernel_sources():
 
 def test_committed_pmc_summary_matches_this_build():
     """roofline.traffic of the driver's bench line comes from profiles/*_pmc_hbm.json and is refused when that file measured other kernel
-    sources.  A tree whose csrc/ changed after the last collection skips here (a reminder, not a failure): re-run tools/gpu/r6_final.sh
-    and commit its pmc_hbm.json."""
+    sources.  A tree whose csrc/ changed after the last collection skips here (a reminder, not a failure): collect the counters again
+    by the recipe in DESIGN.md ("PMC summary of the C3 join") and commit the pmc_hbm.json that tools/pmc_hbm_json.py writes."""
     sys.path.insert(0, ROOT)
     import bench
     import pytest

@@ -19,4 +19,4 @@ for it in range(3):
         lib.gdf_amd_profile_reset(); lib.gdf_amd_profile_enable(1)
     assert lib.gdf_amd_debug_partition(C.byref(col.c), fb, ok.data_ptr(), oi.data_ptr(), off, C.byref(nj), info)==0
 p=read_profile(gdf)
-print(os.environ.get('GDF_JK_SDBG','0'), {k:round(v[0]/v[1],3) for k,v in p.items() if v[0]/v[1]>0.05})
+print({k:round(v[0]/v[1],3) for k,v in p.items() if v[0]/v[1]>0.05})
