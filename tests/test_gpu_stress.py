@@ -236,5 +236,23 @@ def test_partition_scan_filter_random_sizes(gdf):
         bounds = np.append(offs, n)
         got_part = np.repeat(np.arange(P), np.diff(bounds))
         np.testing.assert_array_equal(part[ov], got_part, err_msg=str((it, n, P)))
+        # comparison against a scalar, then stencil compaction: data and stencil start at independent offsets inside larger allocations
+        fdt = [np.int8, np.int16, np.int32, np.int64, np.float32, np.float64][int(rng.integers(0, 6))]
+        d_off, s_off = int(rng.integers(0, 4)), int(rng.integers(0, 4))
+        keep = [0.01, 0.3, 0.9][int(rng.integers(0, 3))]
+        x = rng.integers(0, 100, size=n).astype(fdt)
+        threshold = np.dtype(fdt).type(round(keep * 100))
+        tx = torch.empty(n + 4, dtype=getattr(torch, np.dtype(fdt).name), device="cuda")
+        tx[d_off:d_off + n] = torch.from_numpy(x)
+        cx = Column(tx[d_off:d_off + n])
+        st = gdf.api.comparison(cx, threshold, 2)                      # GDF_LESS_THAN: about `keep` of the rows
+        tag = (it, n, np.dtype(fdt).name, d_off, s_off, keep)
+        np.testing.assert_array_equal(st.to_numpy().astype(bool), x < threshold, err_msg=str(tag))
+        ts = torch.empty(n + 4, dtype=torch.int8, device="cuda")
+        ts[s_off:s_off + n] = st.data[:n]
+        out = gdf.api.apply_stencil(cx, Column(ts[s_off:s_off + n]))
+        exp = x[x < threshold]
+        assert out.size == len(exp), (tag, out.size, len(exp))
+        np.testing.assert_array_equal(out.to_numpy(), exp, err_msg=str(tag))
         it += 1
     assert it >= 2

@@ -160,6 +160,44 @@ def test_filter_known_answer(sqls):
     assert len(idx) == f["expected_size"] and list(idx) == f["expected_indices"]
 
 
+def test_comparison_conversions_known_answers():
+    """oracle.comparison on answers derived by hand from C's usual arithmetic conversions (the GPU tests compare the kernels with it on
+    exactly these values, so it must not be right only by agreeing with them).  Operators in enum order: ==, !=, <, <=, >, >=."""
+    def cmp(l, r):
+        return [int(oracle.comparison(np.array([l]), np.array([r]), op)[0]) for op in range(6)]
+
+    EQUAL, LESS, GREATER, UNORDERED = [1, 0, 0, 1, 0, 1], [0, 1, 1, 1, 0, 0], [0, 1, 0, 0, 1, 1], [0, 1, 0, 0, 0, 0]
+    # (int32, float32) compares in float32: 2^24 + 1 lies half way between 2^24 and 2^24 + 2 and rounds to the even mantissa, 2^24
+    assert cmp(np.int32(2**24 + 1), np.float32(2**24)) == EQUAL
+    assert cmp(np.float32(2**24), np.int32(2**24 + 1)) == EQUAL
+    assert cmp(np.int32(2**24 + 2), np.float32(2**24)) == GREATER          # (2^24 + 2 is a float32)
+    # (int64, float64) compares in float64: 2^53 + 1 rounds to 2^53
+    assert cmp(np.int64(2**53 + 1), np.float64(2**53)) == EQUAL
+    assert cmp(np.int64(2**53 + 2), np.float64(2**53)) == GREATER
+    # (int64, float32) compares in float32 -- numpy's own promotion would be float64, where 2^24 + 1 is exact and greater
+    assert cmp(np.int64(2**24 + 1), np.float32(2**24)) == EQUAL
+    assert cmp(np.float32(2**24), np.int64(2**24 + 1)) == EQUAL
+    assert cmp(np.int64(2**24 + 1), np.float64(2**24)) == GREATER
+    # ... and to nearest EVEN: 2^24 + 3 lies half way between 2^24 + 2 (odd mantissa) and 2^24 + 4 (even) and goes up
+    assert cmp(np.int64(2**24 + 3), np.float32(2**24 + 4)) == EQUAL
+    assert cmp(np.int64(2**24 + 3), np.float32(2**24 + 2)) == GREATER
+    assert cmp(np.int64(2**63 - 1), np.float32(2.0**63)) == EQUAL           # the int64 maximum rounds up to 2^63
+    # integers of two widths compare by value (sign extension)
+    assert cmp(np.int8(-128), np.int64(-128)) == EQUAL
+    assert cmp(np.int8(-1), np.int32(2**31 - 1)) == LESS
+    assert cmp(np.int64(-(2**63)), np.int8(-128)) == LESS
+    # NaN is unordered: only != holds, whichever side holds it and whatever the other type
+    for nan in (np.float32(np.nan), np.float64(np.nan)):
+        for other in (np.int8(0), np.int64(2**62), np.float32(np.inf), np.float64(-0.0), nan):
+            assert cmp(nan, other) == UNORDERED and cmp(other, nan) == UNORDERED
+    # the two zeros are equal
+    for f in (np.float32, np.float64):
+        assert cmp(f(-0.0), f(0.0)) == EQUAL and cmp(f(0.0), f(-0.0)) == EQUAL
+        assert cmp(f(-0.0), np.int32(0)) == EQUAL
+    # a scalar right-hand side converts like a column
+    assert list(oracle.comparison(np.array([2**24 + 1, 2**24 + 3], dtype=np.int64), np.float32(2**24), 0)) == [1, 0]
+
+
 def test_prefixsum_matches_numpy_statement():
     for dt in (np.int8, np.int32, np.int64):
         for n in (1, 2, 13, 64, 100, 1000):           # python/tests/test_prefixsum.py:16-62
