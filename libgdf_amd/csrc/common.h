@@ -25,7 +25,7 @@
     if (_e != hipSuccess) { gdf_amd::note_hip_error(_e, #call, __FILE__, __LINE__); return GDF_CUDA_ERROR; } \
   } while (0)
 #define RMM_TRY(call)   do { if ((call) != RMM_SUCCESS) return GDF_MEMORYMANAGER_ERROR; } while (0)
-#define GDF_TRY(call)   do { gdf_error _g = (call); if (_g != GDF_SUCCESS) return _g; } while (0)
+#define GDF_TRY(...)    do { gdf_error _g = (__VA_ARGS__); if (_g != GDF_SUCCESS) return _g; } while (0)
 #define GDF_REQUIRE(cond, err) do { if (!(cond)) return (err); } while (0)
 #define HIP_CHECK_LAST() HIP_TRY(hipGetLastError())
 

@@ -26,6 +26,7 @@
 // output dtype (groupby.cuh:308-328), any valid mask -> GDF_VALIDITY_UNSUPPORTED
 // (sqls_ops.cu:1103-1106), empty input -> all output sizes 0, out_col_indices ignored.
 #include "internal.h"
+#include "launch.h"
 
 #include <cstdlib>
 #include <vector>
@@ -2597,22 +2598,12 @@ static gdf_error gb_path_direct(GbJob &j, bool *done) {
       const size_t dlds = (size_t)d.total * 12 + 16;
       const int fastkey = ncols == 1 && (t.col[0].width == 8 || t.col[0].width == 4) ? t.col[0].width : 0;
       const int fastval = (op != OP_COUNT && (in_kind == K_I64 || in_kind == K_F64)) ? 8 : ((op != OP_COUNT && (in_kind == K_I32 || in_kind == K_F32)) ? 4 : 0);
-#define GB_DIRECT_LAUNCH(FK, FV)                                                                                             \
-  do {                                                                                                                       \
-    HIP_TRY(hipFuncSetAttribute((const void *)gb_direct_aggregate<FK, FV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds)); \
-    GDF_LAUNCH("gb_direct_aggregate", (gb_direct_aggregate<FK, FV>), dim3(agrid), dim3(GB_DENSE_THREADS), dlds, stream0(), t, d, val, op, \
-               gacc.as<unsigned long long>(), gcnt.as<unsigned long long>(), achunk, ng.as<unsigned int>() + 1);             \
-  } while (0)
-      if (fastkey == 8 && fastval == 8) GB_DIRECT_LAUNCH(8, 8);
-      else if (fastkey == 8 && fastval == 4) GB_DIRECT_LAUNCH(8, 4);
-      else if (fastkey == 8) GB_DIRECT_LAUNCH(8, 0);
-      else if (fastkey == 4 && fastval == 8) GB_DIRECT_LAUNCH(4, 8);
-      else if (fastkey == 4 && fastval == 4) GB_DIRECT_LAUNCH(4, 4);
-      else if (fastkey == 4) GB_DIRECT_LAUNCH(4, 0);
-      else if (fastval == 8) GB_DIRECT_LAUNCH(0, 8);
-      else if (fastval == 4) GB_DIRECT_LAUNCH(0, 4);
-      else GB_DIRECT_LAUNCH(0, 0);
-#undef GB_DIRECT_LAUNCH
+      GDF_TRY(with_int<8, 4, 0>(fastkey, [&](auto FK) {
+        return with_int<8, 4, 0>(fastval, [&](auto FV) {
+          return launch_lds("gb_direct_aggregate", gb_direct_aggregate<FK(), FV()>, dim3(agrid), dim3(GB_DENSE_THREADS), dlds, t, d, val, op,
+                            gacc.as<unsigned long long>(), gcnt.as<unsigned long long>(), achunk, ng.as<unsigned int>() + 1);
+        });
+      }));
       GbOut o{};
       o.ncols = ncols;
       for (int c = 0; c < ncols; ++c) o.key_out[c] = out_keys[c]->data;
@@ -2624,8 +2615,7 @@ static gdf_error gb_path_direct(GbJob &j, bool *done) {
         RMM_TRY(glast.alloc(sizeof(unsigned int) * d.total));
         HIP_TRY(hipMemsetAsync(glast.p, 0, sizeof(unsigned int) * d.total, stream0()));
         const size_t llds = (size_t)d.total * 4 + 16;
-        HIP_TRY(hipFuncSetAttribute((const void *)gb_direct_last_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds));
-        GDF_LAUNCH("gb_direct_last_rows", gb_direct_last_rows, dim3(agrid), dim3(GB_DENSE_THREADS), llds, stream0(), t, d, glast.as<unsigned int>(), achunk);
+        GDF_TRY(launch_lds("gb_direct_last_rows", gb_direct_last_rows, dim3(agrid), dim3(GB_DENSE_THREADS), llds, t, d, glast.as<unsigned int>(), achunk));
         o.indices = j.sort_indices;
         o.last_rows = glast.as<unsigned int>();
       }
@@ -2718,9 +2708,9 @@ static gdf_error gb_path_dense(GbJob &j, bool *done) {
       const int egrid = stream_grid((size_t)n, GB_LD_THREADS * GB_DENSE_BATCH, NUM_CU);
       const int64_t echunk = (((n + egrid - 1) / egrid) + GB_LD_THREADS - 1) / GB_LD_THREADS * GB_LD_THREADS;
       const size_t ilds = sizeof(uint32_t) * GB_LD_SLOTS + sizeof(uint64_t) * GB_LD_MAX_GROUPS;
-      HIP_TRY(hipFuncSetAttribute((const void *)gb_ld_image, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds));
-      HIP_TRY(hipFuncSetAttribute((const void *)gb_ld_encode<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds));
-      HIP_TRY(hipFuncSetAttribute((const void *)gb_ld_encode<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds));
+      GDF_TRY(allow_lds(gb_ld_image, ilds));
+      GDF_TRY(allow_lds(gb_ld_encode<true>, ilds));
+      GDF_TRY(allow_lds(gb_ld_encode<false>, ilds));
       for (int round = 0; round < 2; ++round) {                    // round 1 only if round 0 met keys the sample had not
         if (round) HIP_TRY(hipMemsetAsync(ld_state, 0, sizeof(unsigned int) * 4, stream0()));      // [4] = the numbering counter
         GDF_LAUNCH("gb_dict_number", gb_dict_number, dim3(stream_grid(T + 1, 256 * 4)), dim3(256), 0, stream0(), g, 0xffffffffu,
@@ -2773,32 +2763,22 @@ static gdf_error gb_path_dense(GbJob &j, bool *done) {
       const int64_t achunk = (((n + agrid - 1) / agrid) + GB_DENSE_THREADS - 1) / GB_DENSE_THREADS * GB_DENSE_THREADS;
       const size_t dlds = (size_t)ngroups * (avg ? 12 : 8) + 16;
       const bool fastval = !masked && op != OP_COUNT && kind_width(in_kind) == 8;
-#define GB_DENSE_LAUNCH(FK, FV, MK)                                                                                          \
-  do {                                                                                                                       \
-    HIP_TRY(hipFuncSetAttribute((const void *)gb_dense_aggregate<FK, FV, MK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds)); \
-    GDF_LAUNCH("gb_dense_aggregate", (gb_dense_aggregate<FK, FV, MK>), dim3(agrid), dim3(GB_DENSE_THREADS), dlds, stream0(), t, plan, val, \
-               op, g, ngroups, gacc.as<unsigned long long>(), gcnt.as<unsigned long long>(), achunk);                        \
-  } while (0)
       if (have_ids) {
         const int fv = op == OP_COUNT ? 0 : (kind_width(in_kind) == 8 ? 8 : (kind_width(in_kind) == 4 ? 4 : 0));
         const int lgrid = stream_grid((size_t)n, GB_LD_THREADS * GB_DENSE_BATCH, NUM_CU);
         const int64_t lchunk = (((n + lgrid - 1) / lgrid) + GB_LD_THREADS - 1) / GB_LD_THREADS * GB_LD_THREADS;
-#define GB_LD_LAUNCH(FV)                                                                                                     \
-  do {                                                                                                                       \
-    HIP_TRY(hipFuncSetAttribute((const void *)gb_ld_aggregate<FV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds)); \
-    GDF_LAUNCH("gb_ld_aggregate", gb_ld_aggregate<FV>, dim3(lgrid), dim3(GB_LD_THREADS), dlds, stream0(), val, op, ids.as<uint16_t>(), n, \
-               ngroups, gacc.as<unsigned long long>(), gcnt.as<unsigned long long>(), lchunk);                               \
-  } while (0)
-        if (fv == 8) GB_LD_LAUNCH(8);
-        else if (fv == 4) GB_LD_LAUNCH(4);
-        else GB_LD_LAUNCH(0);
-#undef GB_LD_LAUNCH
-      } else if (masked) GB_DENSE_LAUNCH(false, false, true);
-      else if (fastkey && fastval) GB_DENSE_LAUNCH(true, true, false);
-      else if (fastkey) GB_DENSE_LAUNCH(true, false, false);
-      else if (fastval) GB_DENSE_LAUNCH(false, true, false);
-      else GB_DENSE_LAUNCH(false, false, false);
-#undef GB_DENSE_LAUNCH
+        GDF_TRY(with_int<8, 4, 0>(fv, [&](auto FV) {
+          return launch_lds("gb_ld_aggregate", gb_ld_aggregate<FV()>, dim3(lgrid), dim3(GB_LD_THREADS), dlds, val, op, ids.as<uint16_t>(), n, ngroups,
+                            gacc.as<unsigned long long>(), gcnt.as<unsigned long long>(), lchunk);
+        }));
+      } else {
+        auto dense = [&](auto kernel) {
+          return launch_lds("gb_dense_aggregate", kernel, dim3(agrid), dim3(GB_DENSE_THREADS), dlds, t, plan, val, op, g, ngroups,
+                            gacc.as<unsigned long long>(), gcnt.as<unsigned long long>(), achunk);
+        };
+        if (masked) GDF_TRY(dense(gb_dense_aggregate<false, false, true>));      // (a masked relation has neither fast path)
+        else GDF_TRY(with_bools([&](auto FK, auto FV) { return dense(gb_dense_aggregate<FK(), FV(), false>); }, fastkey, fastval));
+      }
       GbOut o{};
       o.ncols = ncols;
       for (int c = 0; c < ncols; ++c) o.key_out[c] = out_keys[c]->data;
@@ -3076,32 +3056,28 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
       auto run_scatter = [&]() -> gdf_error {
       if (sig) {
         const int vm = vbit ? 2 : (val.valid ? 1 : 0);        // 0: no mask, 1: mask, 2: mask + validity bit in the key
-        auto scatter = [&](auto kernel) -> gdf_error {
-          HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
-          GDF_LAUNCH(is_hot ? "gbp_scatter_hot" : "gbp_scatter", kernel, sgrid, dim3(GBP_SC_THREADS), slds, stream0(), t, sp, val, fold_op, low, P, chunk,
-                     launch_chunks, (const uint32_t *)hist.as<uint32_t>(), ka.as<GbRec>(), d_flags.as<unsigned int>(), qstride, cstride, hot, spec);
-          return GDF_SUCCESS;
+        auto scatter = [&](auto kernel) {
+          return launch_lds(is_hot ? "gbp_scatter_hot" : "gbp_scatter", kernel, sgrid, dim3(GBP_SC_THREADS), slds, t, sp, val, fold_op, low, P, chunk,
+                            launch_chunks, hist.as<uint32_t>(), ka.as<GbRec>(), d_flags.as<unsigned int>(), qstride, cstride, hot, spec);
         };
-#define GBP_SIG(K0, K1)                                                                                                          \
-        if (k0 == K0 && k1 == K1) {                                                                                                 \
-          if (vm == 2 && is_hot && is_spec) GDF_TRY(scatter(gbp_scatter_static<true, K0, K1, true, true, true>));                  \
-          else if (vm == 0 && is_hot && is_spec) GDF_TRY(scatter(gbp_scatter_static<false, K0, K1, false, true, true>));           \
-          else if (vm == 2 && is_spec) GDF_TRY(scatter(gbp_scatter_static<true, K0, K1, true, false, true>));                      \
-          else if (vm == 0 && is_spec) GDF_TRY(scatter(gbp_scatter_static<false, K0, K1, false, false, true>));                    \
-          else if (vm == 2 && is_hot) GDF_TRY(scatter(gbp_scatter_static<true, K0, K1, true, true>));                              \
-          else if (vm == 0 && is_hot) GDF_TRY(scatter(gbp_scatter_static<false, K0, K1, false, true>));                            \
-          else if (vm == 2) GDF_TRY(scatter(gbp_scatter_static<true, K0, K1, true>));                                              \
-          else if (vm == 1) GDF_TRY(scatter(gbp_scatter_static<false, K0, K1, true>));                                             \
-          else GDF_TRY(scatter(gbp_scatter_static<false, K0, K1, false>));                                                         \
-        }
-        GBP_SIG(K_I32, -2) GBP_SIG(K_I64, -2) GBP_SIG(K_I32, K_I32) GBP_SIG(K_I32, K_I64) GBP_SIG(K_I64, K_I32) GBP_SIG(K_I64, K_I64)
-#undef GBP_SIG
+        // gbp_scatter_static<VBIT, K0, K1, VMASK, HOT, SPEC>: every key signature, the nine (mask, hot, spec) combinations that exist
+        GDF_TRY(with_int<K_I32, K_I64>(k0, [&](auto K0) {
+          return with_int<-2, K_I32, K_I64>(k1, [&](auto K1) {
+            if (vm == 2 && is_hot && is_spec) return scatter(gbp_scatter_static<true, K0(), K1(), true, true, true>);
+            if (vm == 0 && is_hot && is_spec) return scatter(gbp_scatter_static<false, K0(), K1(), false, true, true>);
+            if (vm == 2 && is_spec) return scatter(gbp_scatter_static<true, K0(), K1(), true, false, true>);
+            if (vm == 0 && is_spec) return scatter(gbp_scatter_static<false, K0(), K1(), false, false, true>);
+            if (vm == 2 && is_hot) return scatter(gbp_scatter_static<true, K0(), K1(), true, true>);
+            if (vm == 0 && is_hot) return scatter(gbp_scatter_static<false, K0(), K1(), false, true>);
+            if (vm == 2) return scatter(gbp_scatter_static<true, K0(), K1(), true>);
+            if (vm == 1) return scatter(gbp_scatter_static<false, K0(), K1(), true>);
+            return scatter(gbp_scatter_static<false, K0(), K1(), false>);
+          });
+        }));
       } else {
-        auto scatter = [&](auto kernel) -> gdf_error {
-          HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
-          GDF_LAUNCH("gbp_scatter", kernel, sgrid, dim3(GBP_SC_THREADS), slds, stream0(), t, sp, val, fold_op, low, part_bits, P, chunk, launch_chunks,
-                     (const uint32_t *)hist.as<uint32_t>(), ka.as<GbRec>(), qstride, cstride);
-          return GDF_SUCCESS;
+        auto scatter = [&](auto kernel) {
+          return launch_lds("gbp_scatter", kernel, sgrid, dim3(GBP_SC_THREADS), slds, t, sp, val, fold_op, low, part_bits, P, chunk, launch_chunks,
+                            hist.as<uint32_t>(), ka.as<GbRec>(), qstride, cstride);
         };
         if (vbit) GDF_TRY(scatter(gbp_scatter<true>));
         else GDF_TRY(scatter(gbp_scatter<false>));
@@ -3224,34 +3200,21 @@ static gdf_error gb_sorted_partitioned(GbJob &j, const GbKeyPlan &sp, int vbit, 
     }
     const size_t plds = (((size_t)1 << id_bits) + GB_PART_TRASH) * (vbit ? 16 : 12) + 16;
     bool launched = units.empty();          // (every row in the hot window: the scatter kernel aggregated them all)
+    // gb_part_aggregate<VBIT, K, REC>: REC (the fused record layout) exists for 4-byte keys only
+    auto aggregate = [&](auto REC, const uint64_t *payload, const GbSpec &layout) {
+      return with_bools([&](auto V) {
+        return launch_lds("gb_part_aggregate", gb_part_aggregate<V(), K, REC()>, dim3((unsigned)units.size()), dim3(GB_DENSE_THREADS), plds, (const K *)kin, payload,
+                          d_units.as<GbPartUnit>(), id_bits, fold_op, flt, gacc.as<unsigned long long>(), grows.as<unsigned int>(),
+                          vbit ? gvalid.as<unsigned int>() : nullptr, layout);
+      }, vbit != 0);
+    };
     if constexpr (sizeof(K) == 4) {
       if (fused && !launched) {
         launched = true;
-        if (vbit) {
-          HIP_TRY(hipFuncSetAttribute((const void *)gb_part_aggregate<true, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
-          GDF_LAUNCH("gb_part_aggregate", (gb_part_aggregate<true, K, true>), dim3((unsigned)units.size()), dim3(GB_DENSE_THREADS), plds, stream0(),
-                     (const K *)kin, (const uint64_t *)nullptr, (const GbPartUnit *)d_units.as<GbPartUnit>(), id_bits, fold_op, flt,
-                     gacc.as<unsigned long long>(), grows.as<unsigned int>(), gvalid.as<unsigned int>(), aggregate_spec);
-        } else {
-          HIP_TRY(hipFuncSetAttribute((const void *)gb_part_aggregate<false, K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
-          GDF_LAUNCH("gb_part_aggregate", (gb_part_aggregate<false, K, true>), dim3((unsigned)units.size()), dim3(GB_DENSE_THREADS), plds, stream0(),
-                     (const K *)kin, (const uint64_t *)nullptr, (const GbPartUnit *)d_units.as<GbPartUnit>(), id_bits, fold_op, flt,
-                     gacc.as<unsigned long long>(), grows.as<unsigned int>(), (unsigned int *)nullptr, aggregate_spec);
-        }
+        GDF_TRY(aggregate(std::true_type{}, nullptr, aggregate_spec));
       }
     }
-    if (launched) {
-    } else if (vbit) {
-      HIP_TRY(hipFuncSetAttribute((const void *)gb_part_aggregate<true, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
-      GDF_LAUNCH("gb_part_aggregate", (gb_part_aggregate<true, K>), dim3((unsigned)units.size()), dim3(GB_DENSE_THREADS), plds, stream0(), (const K *)kin,
-                 (const uint64_t *)pin, (const GbPartUnit *)d_units.as<GbPartUnit>(), id_bits, fold_op, flt, gacc.as<unsigned long long>(),
-                 grows.as<unsigned int>(), gvalid.as<unsigned int>(), GbSpec{});
-    } else {
-      HIP_TRY(hipFuncSetAttribute((const void *)gb_part_aggregate<false, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
-      GDF_LAUNCH("gb_part_aggregate", (gb_part_aggregate<false, K>), dim3((unsigned)units.size()), dim3(GB_DENSE_THREADS), plds, stream0(), (const K *)kin,
-                 (const uint64_t *)pin, (const GbPartUnit *)d_units.as<GbPartUnit>(), id_bits, fold_op, flt, gacc.as<unsigned long long>(),
-                 grows.as<unsigned int>(), (unsigned int *)nullptr, GbSpec{});
-    }
+    if (!launched) GDF_TRY(aggregate(std::false_type{}, (const uint64_t *)pin, GbSpec{}));
     const unsigned nblocks = (unsigned)(cells_pad / 1024);
     GDF_LAUNCH("gb_part_count", gb_part_count, dim3(nblocks), dim3(1024), 0, stream0(), (const unsigned int *)grows.as<unsigned int>(), bcnt.as<uint32_t>());
     DevBuf scan_scratch;
@@ -3422,8 +3385,7 @@ static gdf_error gb_path_table(GbJob &j) {
     g.limit = T >= cap_max ? 0xffffffffu : (uint32_t)(T / 2);   // at 2*N slots the table can never fill
     GDF_LAUNCH("gb_init_table", gb_init_table, dim3(stream_grid(T + 1, 256 * 8)), dim3(256), 0, stream0(), g, op == OP_AVG ? OP_SUM : op, plan.packed);
     if (plan.packed) {
-      HIP_TRY(hipFuncSetAttribute((const void *)gb_aggregate<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      GDF_LAUNCH("gb_aggregate_packed", gb_aggregate<true>, dim3(grid), dim3(GB_THREADS), lds, stream0(), t, plan, val, op, g, chunk);
+      GDF_TRY(launch_lds("gb_aggregate_packed", gb_aggregate<true>, dim3(grid), dim3(GB_THREADS), lds, t, plan, val, op, g, chunk));
     } else {
       GDF_LAUNCH("gb_aggregate_rows", gb_aggregate<false>, dim3(grid), dim3(GB_THREADS), 0, stream0(), t, plan, val, op, g, chunk);
     }

@@ -21,6 +21,7 @@
 // increasing p; order inside a partition is unspecified.
 #include "hash.cuh"
 #include "internal.h"
+#include "launch.h"
 #include "gdf/gdf_amd_ext.h"
 
 #include <cstdlib>
@@ -1153,39 +1154,35 @@ static gdf_error hash_partition_two_level(int ncols, gdf_column *input[], const 
   PartLevel la{};
   la.mode = 1; la.kshift = kshift; la.hashP = P; la.hashmask = pow2mask;
   const size_t ldsA = sizeof(uint32_t) * S * K;
-#define HP2_HIST(NAME, LV, TAB, NBINS, NCH, CHUNK, GRID, LDS, OUT)                                                                              \
-  do {                                                                                                                                    \
-    if (fastw == 8) { HIP_TRY(hipFuncSetAttribute((const void *)part_hist_fast_kernel<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS))); \
-      GDF_LAUNCH(NAME, part_hist_fast_kernel<uint64_t>, dim3(GRID), dim3(HP_THREADS), LDS, stream0(), (const uint64_t *)TAB.col[0].data, n, CHUNK, NCH, NBINS, 0u, -1, OUT, LV); } \
-    else if (fastw == 4) { HIP_TRY(hipFuncSetAttribute((const void *)part_hist_fast_kernel<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS))); \
-      GDF_LAUNCH(NAME, part_hist_fast_kernel<uint32_t>, dim3(GRID), dim3(HP_THREADS), LDS, stream0(), (const uint32_t *)TAB.col[0].data, n, CHUNK, NCH, NBINS, 0u, -1, OUT, LV); } \
-    else if (murmur) { HIP_TRY(hipFuncSetAttribute((const void *)part_hist_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS))); \
-      GDF_LAUNCH(NAME, part_hist_kernel<true>, dim3(GRID), dim3(HP_THREADS), LDS, stream0(), TAB, n, CHUNK, NCH, NBINS, 0u, OUT, LV); } \
-    else { HIP_TRY(hipFuncSetAttribute((const void *)part_hist_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS))); \
-      GDF_LAUNCH(NAME, part_hist_kernel<false>, dim3(GRID), dim3(HP_THREADS), LDS, stream0(), TAB, n, CHUNK, NCH, NBINS, 0u, OUT, LV); } \
-  } while (0)
-  HP2_HIST("part_hist", lh, t, S * K, nchunks, chunk, grid, ldsA, histA.as<uint32_t>());
+  if (fastw == 8)
+    GDF_TRY(launch_lds("part_hist", part_hist_fast_kernel<uint64_t>, dim3(grid), dim3(HP_THREADS), ldsA, (const uint64_t *)t.col[0].data, n, chunk, nchunks, S * K, 0u, -1, histA.as<uint32_t>(), lh));
+  else if (fastw == 4)
+    GDF_TRY(launch_lds("part_hist", part_hist_fast_kernel<uint32_t>, dim3(grid), dim3(HP_THREADS), ldsA, (const uint32_t *)t.col[0].data, n, chunk, nchunks, S * K, 0u, -1, histA.as<uint32_t>(), lh));
+  else
+    GDF_TRY(with_bools([&](auto MUR) {
+      return launch_lds("part_hist", part_hist_kernel<MUR()>, dim3(grid), dim3(HP_THREADS), ldsA, t, n, chunk, nchunks, S * K, 0u, histA.as<uint32_t>(), lh);
+    }, murmur));
   HIP_CHECK_LAST();
-#undef HP2_HIST
   GDF_TRY(scan_u32(histA.as<uint32_t>(), histA.as<uint32_t>(), histA_words, false));      // [s][chunk] + the total: level-A offsets AND the pieces' row ranges
   // level B's histogram: (partition, piece) = the partition's counts over the piece's level-A chunks; index partition * M + piece
   GDF_LAUNCH("hpt_piece_counts", hpt_piece_counts, dim3((unsigned)((histB_words + 255) / 256)), dim3(256), 0, stream0(), (const uint32_t *)histFull.as<uint32_t>(),
              histB.as<uint32_t>(), (uint32_t)(S * K), (uint32_t)nchunks, group, M);
   HIP_CHECK_LAST();
   GDF_TRY(scan_u32(histB.as<uint32_t>(), histB.as<uint32_t>(), histB_words, false));
-#define HP2_TILE(NAME, MUR, FW, TH, MAXP, FI, TAB, NBINS, NCH, CHUNK, GRID, OFFS, LV)                                                           \
-  do {                                                                                                                                    \
-    const size_t l2 = HptShape<TH, MAXP, FI, (FW) != 0>::lds_bytes();                                                                    \
-    HIP_TRY(hipFuncSetAttribute((const void *)part_scatter_tile_kernel<MUR, FW, TH, MAXP, FI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2)); \
-    GDF_LAUNCH(NAME, (part_scatter_tile_kernel<MUR, FW, TH, MAXP, FI>), dim3(GRID), dim3(TH), l2, stream0(), TAB, pc, n, CHUNK, NCH, NBINS, 0u, OFFS, LV); \
-  } while (0)
+  // part_scatter_tile_kernel<murmur, fast key width, 1024 threads x 12 rows>: the four (murmur, width) pairs that exist
+  auto tile_pass = [&](const char *name, const KeyTable &tab, const PayloadCols &pc, uint32_t nbins, int nch, int64_t chunk_rows, int tgrid, const uint32_t *offs,
+                       const PartLevel &lv) -> gdf_error {
+    auto launch = [&](auto kernel, size_t l2) { return launch_lds(name, kernel, dim3(tgrid), dim3(1024), l2, tab, pc, n, chunk_rows, nch, nbins, 0u, offs, lv); };
+    if (fastw == 8) GDF_TRY(launch(part_scatter_tile_kernel<true, 8, 1024, 1024, 12>, HptShape<1024, 1024, 12, true>::lds_bytes()));
+    else if (fastw == 4) GDF_TRY(launch(part_scatter_tile_kernel<true, 4, 1024, 1024, 12>, HptShape<1024, 1024, 12, true>::lds_bytes()));
+    else if (murmur) GDF_TRY(launch(part_scatter_tile_kernel<true, 0, 1024, 1024, 12>, HptShape<1024, 1024, 12, false>::lds_bytes()));
+    else GDF_TRY(launch(part_scatter_tile_kernel<false, 0, 1024, 1024, 12>, HptShape<1024, 1024, 12, false>::lds_bytes()));
+    HIP_CHECK_LAST();
+    return GDF_SUCCESS;
+  };
   {
     PayloadCols pc = payload(input, tmp_ptr.data(), false);
-    if (fastw == 8) HP2_TILE("part_scatter", true, 8, 1024, 1024, 12, t, S, nchunks, chunk, grid, histA.as<uint32_t>(), la);
-    else if (fastw == 4) HP2_TILE("part_scatter", true, 4, 1024, 1024, 12, t, S, nchunks, chunk, grid, histA.as<uint32_t>(), la);
-    else if (murmur) HP2_TILE("part_scatter", true, 0, 1024, 1024, 12, t, S, nchunks, chunk, grid, histA.as<uint32_t>(), la);
-    else HP2_TILE("part_scatter", false, 0, 1024, 1024, 12, t, S, nchunks, chunk, grid, histA.as<uint32_t>(), la);
-    HIP_CHECK_LAST();
+    GDF_TRY(tile_pass("part_scatter", t, pc, S, nchunks, chunk, grid, histA.as<uint32_t>(), la));
   }
   // ---- level B: S x M pieces of the temporary table, K bins each, the level-A tile shape (1024 threads x 12 rows: one workgroup per
   // CU with sixteen waves; 256-thread tiles left a CU with two workgroups of four waves, 1.18 vs 0.86 ms).  The scan of
@@ -1200,13 +1197,8 @@ static gdf_error hash_partition_two_level(int ncols, gdf_column *input[], const 
     HIP_TRY(clear_err);
     for (int k = 0; k < ncols; ++k)
       if (input[k]->valid && output[k]->valid) output[k]->null_count = input[k]->null_count;
-    if (fastw == 8) HP2_TILE("part_scatter_b", true, 8, 1024, 1024, 12, t2, K, nchunksB, (int64_t)0, gridB, histB.as<uint32_t>(), lb);
-    else if (fastw == 4) HP2_TILE("part_scatter_b", true, 4, 1024, 1024, 12, t2, K, nchunksB, (int64_t)0, gridB, histB.as<uint32_t>(), lb);
-    else if (murmur) HP2_TILE("part_scatter_b", true, 0, 1024, 1024, 12, t2, K, nchunksB, (int64_t)0, gridB, histB.as<uint32_t>(), lb);
-    else HP2_TILE("part_scatter_b", false, 0, 1024, 1024, 12, t2, K, nchunksB, (int64_t)0, gridB, histB.as<uint32_t>(), lb);
-    HIP_CHECK_LAST();
+    GDF_TRY(tile_pass("part_scatter_b", t2, pc, K, nchunksB, 0, gridB, histB.as<uint32_t>(), lb));
   }
-#undef HP2_TILE
   // partition_offsets (HOST array): every M-th entry of the scanned level-B histogram (index partition * M) is a partition's start
   hipLaunchKernelGGL(gather_strided_u32, dim3((P + 255) / 256), dim3(256), 0, stream0(), (const uint32_t *)histB.as<uint32_t>(), d_starts.as<uint32_t>(), (int)P, (size_t)M);
   HIP_CHECK_LAST();
@@ -1533,9 +1525,8 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
     DevBuf dump;
     RMM_TRY(dump.alloc(sizeof(uint64_t) * HPC_THREADS));
     const int pgrid = nchunks < NUM_CU * 4 ? nchunks : NUM_CU * 4;
-    HIP_TRY(hipFuncSetAttribute((const void *)part_scatter_cols8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(HpcLds)));
-    GDF_LAUNCH("part_scatter", part_scatter_cols8_kernel, dim3(pgrid), dim3(HPC_THREADS), sizeof(HpcLds), stream0(), hc, dump.as<uint64_t>(), n, chunk,
-               nchunks, P, pow2mask, (const uint32_t *)hist.as<uint32_t>(), lv0);
+    GDF_TRY(launch_lds("part_scatter", part_scatter_cols8_kernel, dim3(pgrid), dim3(HPC_THREADS), sizeof(HpcLds), hc, dump.as<uint64_t>(), n, chunk,
+                       nchunks, P, pow2mask, hist.as<uint32_t>(), lv0));
     HIP_CHECK_LAST();
     HIP_TRY(hipMemcpyAsync(partition_offsets, starts.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream0()));
     HIP_TRY(hipStreamSynchronize(stream0()));
@@ -1550,16 +1541,13 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
     const uint64_t *ia = (const uint64_t *)input[0]->data, *ib = two ? (const uint64_t *)input[1]->data : nullptr;
     uint64_t *oa = (uint64_t *)partitioned_output[0]->data, *ob = two ? (uint64_t *)partitioned_output[1]->data : nullptr;
     const int pgrid = nchunks < NUM_CU * 4 ? nchunks : NUM_CU * 4;          // (a multiple of 8 when it is not nchunks itself: chunk c runs on XCD c % 8)
-#define HPP_LAUNCH(TWO, KC)                                                                                                            \
-  do {                                                                                                                                 \
-    HIP_TRY(hipFuncSetAttribute((const void *)part_scatter_pairs_kernel<TWO, KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(HppLds))); \
-    GDF_LAUNCH("part_scatter", (part_scatter_pairs_kernel<TWO, KC>), dim3(pgrid), dim3(HPP_THREADS), sizeof(HppLds), stream0(), ia, ib, oa, ob,   \
-               dump.as<uint64_t>(), n, chunk, nchunks, P, pow2mask, (const uint32_t *)hist.as<uint32_t>(), lv0);                        \
-  } while (0)
-    if (!two) HPP_LAUNCH(false, 0);
-    else if (keycol == 0) HPP_LAUNCH(true, 0);
-    else HPP_LAUNCH(true, 1);
-#undef HPP_LAUNCH
+    auto launch = [&](auto kernel) {
+      return launch_lds("part_scatter", kernel, dim3(pgrid), dim3(HPP_THREADS), sizeof(HppLds), ia, ib, oa, ob, dump.as<uint64_t>(), n, chunk, nchunks, P, pow2mask,
+                        hist.as<uint32_t>(), lv0);
+    };
+    if (!two) GDF_TRY(launch(part_scatter_pairs_kernel<false, 0>));
+    else if (keycol == 0) GDF_TRY(launch(part_scatter_pairs_kernel<true, 0>));
+    else GDF_TRY(launch(part_scatter_pairs_kernel<true, 1>));
     HIP_CHECK_LAST();
     HIP_TRY(hipMemcpyAsync(partition_offsets, starts.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream0()));
     HIP_TRY(hipStreamSynchronize(stream0()));
@@ -1597,20 +1585,15 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
     else if (P > 16 && P <= (uint32_t)HPT_BIG_PARTS) {
       // measured at 1e8 rows x 2 int64 columns: P=256 1.47 ms vs 2.83 ms direct; at P=8 the direct kernel's runs are
       // long enough already (1.10 vs 1.19 ms), so small fan-outs keep it
-#define HPT_LAUNCH(MUR, FW, TH, MAXP, FI)                                                                                              \
-  do {                                                                                                                                 \
-    const size_t tl = HptShape<TH, MAXP, FI, (FW) != 0>::lds_bytes();                                                                  \
-    HIP_TRY(hipFuncSetAttribute((const void *)part_scatter_tile_kernel<MUR, FW, TH, MAXP, FI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl)); \
-    GDF_LAUNCH("part_scatter", (part_scatter_tile_kernel<MUR, FW, TH, MAXP, FI>), dim3(grid), dim3(TH), tl, stream0(), t, pc, n, chunk, \
-               nchunks, P, pow2mask, hist.as<uint32_t>(), PartLevel{});                                                                \
-  } while (0)
       // 12288-row tiles of a 1024-thread workgroup: they won over 4096-row tiles of 256 threads at EVERY fan-out the two shared
       // (1e8 rows x 2 int64 columns, scatter kernel: P = 64 0.73 vs 0.88 ms, P = 256 0.82 vs 1.07 ms): three times the run length
-      if (fastw == 8) HPT_LAUNCH(true, 8, 1024, 1024, 12);
-      else if (fastw == 4) HPT_LAUNCH(true, 4, 1024, 1024, 12);
-      else if (murmur) HPT_LAUNCH(true, 0, 1024, 1024, 12);
-      else HPT_LAUNCH(false, 0, 1024, 1024, 12);
-#undef HPT_LAUNCH
+      auto launch = [&](auto kernel, size_t tl) {
+        return launch_lds("part_scatter", kernel, dim3(grid), dim3(1024), tl, t, pc, n, chunk, nchunks, P, pow2mask, hist.as<uint32_t>(), PartLevel{});
+      };
+      if (fastw == 8) GDF_TRY(launch(part_scatter_tile_kernel<true, 8, 1024, 1024, 12>, HptShape<1024, 1024, 12, true>::lds_bytes()));
+      else if (fastw == 4) GDF_TRY(launch(part_scatter_tile_kernel<true, 4, 1024, 1024, 12>, HptShape<1024, 1024, 12, true>::lds_bytes()));
+      else if (murmur) GDF_TRY(launch(part_scatter_tile_kernel<true, 0, 1024, 1024, 12>, HptShape<1024, 1024, 12, false>::lds_bytes()));
+      else GDF_TRY(launch(part_scatter_tile_kernel<false, 0, 1024, 1024, 12>, HptShape<1024, 1024, 12, false>::lds_bytes()));
     } else if (fastw == 8)
       GDF_LAUNCH("part_scatter", part_scatter_fast_kernel<uint64_t>, dim3(grid), dim3(HP_THREADS), lds, stream0(), (const uint64_t *)t.col[0].data, pc, n,
                  chunk, nchunks, P, pow2mask, agg_bits, hist.as<uint32_t>());

@@ -46,6 +46,7 @@
 // (joining.h:58-66), outputs are library-allocated int32 columns of exactly the joined
 // size, pair order unspecified.
 #include "internal.h"
+#include "launch.h"
 #include "gdf/gdf_amd_ext.h"
 
 #include <cmath>
@@ -1537,8 +1538,7 @@ __global__ __launch_bounds__(JK_BK_THREADS) void jk_make_l2map(const uint32_t *_
 }
 static gdf_error l2map_prepare(uint32_t nseg, size_t *lds) {
   *lds = nseg <= JK_L2MAP_LDS_SEGS ? sizeof(uint32_t) * (size_t)nseg : 0;
-  HIP_TRY(hipFuncSetAttribute((const void *)jk_make_l2map, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(uint32_t) * JK_L2MAP_LDS_SEGS)));
-  return GDF_SUCCESS;
+  return allow_lds(jk_make_l2map, sizeof(uint32_t) * JK_L2MAP_LDS_SEGS);
 }
 __global__ __launch_bounds__(256) void jk_init_cursor(uint32_t *cur, uint32_t nfine, uint32_t cap2, const uint32_t *__restrict__ fstart = nullptr) {
   for (uint32_t f = blockIdx.x * 256 + threadIdx.x; f <= nfine; f += gridDim.x * 256) cur[f] = f < nfine ? (fstart ? fstart[f] : f * cap2) : 0u;   // [nfine]: overflow flag
@@ -3196,8 +3196,7 @@ static inline int small_grid(int64_t n) { return stream_grid((size_t)(n > 0 ? n 
 template <int FAST, bool NARROW, int THREADS, bool MASKED>
 static gdf_error launch_scatter1_t(const KeyTable &t, const KeyPlan &plan, const PartGeom &g, const uint32_t *H1off, Tuples out) {
   const size_t lds = sizeof(TileLds<NARROW, THREADS, false, sc1_items(NARROW, THREADS)>);
-  HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter1<FAST, NARROW, THREADS, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  GDF_LAUNCH("jk_scatter1", (jk_scatter1<FAST, NARROW, THREADS, MASKED>), dim3(g.nchunks), dim3(THREADS), lds, stream0(), t, plan, g, H1off, out);
+  GDF_TRY(launch_lds("jk_scatter1", jk_scatter1<FAST, NARROW, THREADS, MASKED>, dim3(g.nchunks), dim3(THREADS), lds, t, plan, g, H1off, out));
   HIP_CHECK_LAST();
   return GDF_SUCCESS;
 }
@@ -3218,27 +3217,17 @@ static gdf_error launch_scatter1(int fast, bool narrow, const KeyTable &t, const
     if (!(fast && g.cap1 && g.xs == 6 && g.b1 == 8) || (!narrow && fast != 8)) return GDF_INVALID_API_CALL;
     if (!narrow) {                   // WIDE keys: the ten-byte tuples (W10, p10_key) -- 12 tuples per thread, 12 bytes per tuple in LDS
       const size_t lds = sizeof(TileLds<false, 1024, false, 12>);
-      if (masked) {
-        HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter1<8, false, 1024, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GDF_LAUNCH("jk_scatter1_w10", (jk_scatter1<8, false, 1024, true, true>), dim3(g.nchunks), dim3(1024), lds, stream0(), t, plan, g, H1off, out);
-      } else {
-        HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter1<8, false, 1024, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GDF_LAUNCH("jk_scatter1_w10", (jk_scatter1<8, false, 1024, false, true>), dim3(g.nchunks), dim3(1024), lds, stream0(), t, plan, g, H1off, out);
-      }
-      HIP_CHECK_LAST();
-      return GDF_SUCCESS;
+      GDF_TRY(with_bools([&](auto M) {
+        return launch_lds("jk_scatter1_w10", jk_scatter1<8, false, 1024, M(), true>, dim3(g.nchunks), dim3(1024), lds, t, plan, g, H1off, out);
+      }, masked));
+    } else {
+      const size_t lds = sizeof(TileLds<true, 1024>);
+      GDF_TRY(with_int<8, 4>(fast, [&](auto F) {
+        return with_bools([&](auto M) {
+          return launch_lds("jk_scatter1", jk_scatter1<F(), true, 1024, M(), true>, dim3(g.nchunks), dim3(1024), lds, t, plan, g, H1off, out);
+        }, masked);
+      }));
     }
-#define JK_SC1_L6(F, M)                                                                                                             \
-    do {                                                                                                                            \
-      const size_t lds = sizeof(TileLds<true, 1024>);                                                                               \
-      HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter1<F, true, 1024, M, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      GDF_LAUNCH("jk_scatter1", (jk_scatter1<F, true, 1024, M, true>), dim3(g.nchunks), dim3(1024), lds, stream0(), t, plan, g, H1off, out); \
-    } while (0)
-    if (fast == 8 && masked) JK_SC1_L6(8, true);
-    else if (fast == 8) JK_SC1_L6(8, false);
-    else if (masked) JK_SC1_L6(4, true);
-    else JK_SC1_L6(4, false);
-#undef JK_SC1_L6
     HIP_CHECK_LAST();
     return GDF_SUCCESS;
   }
@@ -3265,88 +3254,39 @@ static int fast_key_width(const KeyTable &t, const KeyPlan &plan) {
 // LDS of a level-2 tile without the level-1-only arrays at the end of TileLds: three 12-byte-per-tuple tiles per CU instead of two
 template <bool NARROW, int THREADS>
 static constexpr size_t level2_lds_bytes() { using Tile = TileLds<NARROW, THREADS>; return offsetof(Tile, cursor); }
-template <bool NARROW, int THREADS>
-static gdf_error launch_scatter2_t(uint32_t ntiles, const PartGeom &g, Level2Map m, Tuples in, uint32_t *cursor, Tuples out) {
-  const size_t lds = sizeof(TileLds<NARROW, THREADS>);
-  HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<NARROW, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+static gdf_error launch_scatter2(bool narrow, uint32_t ntiles, const PartGeom &g, Level2Map m, Tuples in,
+                                 uint32_t *cursor, Tuples out, bool p6 = false, bool in6 = false, int pw = 1) {
+  if (in6 && !(p6 && !m.keys32 && g.b1 == 8)) return GDF_INVALID_API_CALL;
+  if (!in6 && p6 && !narrow && m.keys32) return GDF_INVALID_API_CALL;
   m.ntiles = ntiles;
   m.xcd_order = (ntiles >= 64 && !lab::path_on("GDF_JK_NO_XCD_ORDER")) ? 1 : 0;
   const uint32_t grid = sc2_grid(m, ntiles);
-  GDF_LAUNCH("jk_scatter2", (jk_scatter2<NARROW, THREADS>), dim3(grid), dim3(THREADS), lds, stream0(), g, m, in, cursor, out);
-  HIP_CHECK_LAST();
-  return GDF_SUCCESS;
-}
-static gdf_error launch_scatter2(bool narrow, uint32_t ntiles, const PartGeom &g, Level2Map m, Tuples in,
-                                 uint32_t *cursor, Tuples out, bool p6 = false, bool in6 = false, int pw = 1) {
+  auto launch = [&](const char *name, auto kernel, int threads, size_t lds) -> gdf_error {
+    GDF_TRY(launch_lds(name, kernel, dim3(grid), dim3(threads), lds, g, m, in, cursor, out));
+    HIP_CHECK_LAST();
+    return GDF_SUCCESS;
+  };
   if (in6) {                         // six-byte level-1 tuples in, six-byte level-2 tuples out
-    if (!(p6 && !m.keys32 && g.b1 == 8)) return GDF_INVALID_API_CALL;
-    m.ntiles = ntiles;
-    m.xcd_order = (ntiles >= 64 && !lab::path_on("GDF_JK_NO_XCD_ORDER")) ? 1 : 0;
-    const uint32_t grid = sc2_grid(m, ntiles);
-    if (!narrow) {                   // ten-byte tuples in and out (WIDE keys)
-      const size_t lds = level2_lds_bytes<false, 256>();
-      HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<false, 256, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      GDF_LAUNCH("jk_scatter2_w10", (jk_scatter2<false, 256, false, true, false, true>), dim3(grid), dim3(256), lds, stream0(), g, m, in, cursor, out);
-      HIP_CHECK_LAST();
-      return GDF_SUCCESS;
-    }
-    const size_t lds = sizeof(TileLds<true, 256>);
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<true, 256, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GDF_LAUNCH("jk_scatter2", (jk_scatter2<true, 256, false, true, false, true>), dim3(grid), dim3(256), lds, stream0(), g, m, in, cursor, out);
-    HIP_CHECK_LAST();
-    return GDF_SUCCESS;
+    if (!narrow)                     // ten-byte tuples in and out (WIDE keys)
+      return launch("jk_scatter2_w10", jk_scatter2<false, 256, 0, true, false, true>, 256, level2_lds_bytes<false, 256>());
+    return launch("jk_scatter2", jk_scatter2<true, 256, 0, true, false, true>, 256, sizeof(TileLds<true, 256>));
   }
-  if (p6 && !narrow) {               // WIDE (key64, row) tuples in, ten-byte tuples out (p10_key): the production tile size
-    if (m.keys32) return GDF_INVALID_API_CALL;
-    m.ntiles = ntiles;
-    m.xcd_order = (ntiles >= 64 && !lab::path_on("GDF_JK_NO_XCD_ORDER")) ? 1 : 0;
-    const uint32_t grid = sc2_grid(m, ntiles);
-    const size_t lds = level2_lds_bytes<false, 256>();
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<false, 256, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GDF_LAUNCH("jk_scatter2_w10", (jk_scatter2<false, 256, false, true>), dim3(grid), dim3(256), lds, stream0(), g, m, in, cursor, out);
-    HIP_CHECK_LAST();
-    return GDF_SUCCESS;
-  }
+  if (p6 && !narrow)                 // WIDE (key64, row) tuples in, ten-byte tuples out (p10_key): the production tile size
+    return launch("jk_scatter2_w10", jk_scatter2<false, 256, 0, true>, 256, level2_lds_bytes<false, 256>());
   if (p6 || m.keys32) {              // six-byte output tuples (see p6_store) and / or a receive buffer of 4-byte keys as input:
-    m.ntiles = ntiles;                 // NARROW, no payload, the production tile size
-    m.xcd_order = (ntiles >= 64 && !lab::path_on("GDF_JK_NO_XCD_ORDER")) ? 1 : 0;
-    const uint32_t grid = sc2_grid(m, ntiles);
-#define JK_SC2_LAUNCH(T, SIX, K)                                                                                                       \
-  do {                                                                                                                                \
-    const size_t lds = sizeof(TileLds<true, T>);                                                                                      \
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<true, T, false, SIX, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    GDF_LAUNCH("jk_scatter2", (jk_scatter2<true, T, false, SIX, K>), dim3(grid), dim3(T), lds, stream0(), g, m, in, cursor, out);      \
-  } while (0)
-    if (p6 && m.keys32) JK_SC2_LAUNCH(256, true, true);
-    else if (p6) JK_SC2_LAUNCH(256, true, false);
-    else JK_SC2_LAUNCH(256, false, true);
-#undef JK_SC2_LAUNCH
-    HIP_CHECK_LAST();
-    return GDF_SUCCESS;
+    const size_t lds = sizeof(TileLds<true, 256>);      // NARROW, no payload, the production tile size
+    if (p6 && m.keys32) return launch("jk_scatter2", jk_scatter2<true, 256, 0, true, true>, 256, lds);
+    if (p6) return launch("jk_scatter2", jk_scatter2<true, 256, 0, true, false>, 256, lds);
+    return launch("jk_scatter2", jk_scatter2<true, 256, 0, false, true>, 256, lds);
   }
   if (narrow && in.pay && pw == 2) { // ... two payload words per tuple (PayCarry mode 4): 2048-tuple tiles of 24 bytes, three workgroups per CU
     using Tile = TileLds<true, 256, 2, JK_PAY_ITEMS>;
-    const size_t lds = offsetof(Tile, cursor);
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<true, 256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    m.ntiles = ntiles;
-    m.xcd_order = (ntiles >= 64 && !lab::path_on("GDF_JK_NO_XCD_ORDER")) ? 1 : 0;
-    const uint32_t grid = sc2_grid(m, ntiles);
-    GDF_LAUNCH("jk_scatter2", (jk_scatter2<true, 256, 2>), dim3(grid), dim3(256), lds, stream0(), g, m, in, cursor, out);
-    HIP_CHECK_LAST();
-    return GDF_SUCCESS;
+    return launch("jk_scatter2", jk_scatter2<true, 256, 2>, 256, offsetof(Tile, cursor));
   }
-  if (narrow && in.pay) {            // a probe side that carries its payload words (PayCarry): the production tile size only
-    const size_t lds = sizeof(TileLds<true, 256, true, JK_PAY_ITEMS>);
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter2<true, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    m.ntiles = ntiles;
-    m.xcd_order = (ntiles >= 64 && !lab::path_on("GDF_JK_NO_XCD_ORDER")) ? 1 : 0;
-    const uint32_t grid = sc2_grid(m, ntiles);
-    GDF_LAUNCH("jk_scatter2", (jk_scatter2<true, 256, true>), dim3(grid), dim3(256), lds, stream0(), g, m, in, cursor, out);
-    HIP_CHECK_LAST();
-    return GDF_SUCCESS;
-  }
-  if (narrow) return launch_scatter2_t<true, JK_SC2_THREADS>(ntiles, g, m, in, cursor, out);
-  return launch_scatter2_t<false, JK_SC2_THREADS>(ntiles, g, m, in, cursor, out);
+  if (narrow && in.pay)              // a probe side that carries its payload words (PayCarry): the production tile size only
+    return launch("jk_scatter2", jk_scatter2<true, 256, 1>, 256, sizeof(TileLds<true, 256, true, JK_PAY_ITEMS>));
+  if (narrow) return launch("jk_scatter2", jk_scatter2<true, JK_SC2_THREADS>, JK_SC2_THREADS, sizeof(TileLds<true, JK_SC2_THREADS>));
+  return launch("jk_scatter2", jk_scatter2<false, JK_SC2_THREADS>, JK_SC2_THREADS, sizeof(TileLds<false, JK_SC2_THREADS>));
 }
 
 // partitions one relation into g.fb-bit fine partitions
@@ -3359,15 +3299,12 @@ static gdf_error launch_scatter2(bool narrow, uint32_t ntiles, const PartGeom &g
 // level-1 scatter of a payload-carrying probe side (jk_scatter1_pay)
 static gdf_error launch_scatter1_pay(int fast, int pmode, const KeyTable &t, const KeyPlan &plan, const PartGeom &g, const uint32_t *H1off,
                                      const PaySrc &ps, Tuples out) {
-#define JK_PAY_LAUNCH(F, M)                                                                                                   \
-  do {                                                                                                                        \
-    const size_t lds = sizeof(TileLds<true, JK_PAY_THREADS, pay_words(M), pay_items1(M)>);                                   \
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_scatter1_pay<F, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    GDF_LAUNCH("jk_scatter1", (jk_scatter1_pay<F, M>), dim3(g.nchunks), dim3(JK_PAY_THREADS), lds, stream0(), t, plan, g, H1off, ps, out); \
-  } while (0)
-  if (fast == 8) { if (pmode == 1) JK_PAY_LAUNCH(8, 1); else if (pmode == 2) JK_PAY_LAUNCH(8, 2); else if (pmode == 3) JK_PAY_LAUNCH(8, 3); else JK_PAY_LAUNCH(8, 4); }
-  else { if (pmode == 1) JK_PAY_LAUNCH(4, 1); else if (pmode == 2) JK_PAY_LAUNCH(4, 2); else if (pmode == 3) JK_PAY_LAUNCH(4, 3); else JK_PAY_LAUNCH(4, 4); }
-#undef JK_PAY_LAUNCH
+  GDF_TRY(with_int<8, 4>(fast, [&](auto F) {
+    return with_int<1, 2, 3, 4>(pmode, [&](auto M) {
+      const size_t lds = sizeof(TileLds<true, JK_PAY_THREADS, pay_words(M()), pay_items1(M())>);
+      return launch_lds("jk_scatter1", jk_scatter1_pay<F(), M()>, dim3(g.nchunks), dim3(JK_PAY_THREADS), lds, t, plan, g, H1off, ps, out);
+    });
+  }));
   HIP_CHECK_LAST();
   return GDF_SUCCESS;
 }
@@ -3401,9 +3338,9 @@ static gdf_error partition_side(const KeyTable &t, KeyPlan &plan, PartGeom g, Si
   const size_t hist_lds = sizeof(uint32_t) * (nfine + ncoarse);
   // FAST: one 8-byte integer key column, no mask -> kernels read the column words directly
   const int fast = fast_key_width(t, plan);
-  HIP_TRY(hipFuncSetAttribute((const void *)jk_hist<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
-  HIP_TRY(hipFuncSetAttribute((const void *)jk_hist<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
-  HIP_TRY(hipFuncSetAttribute((const void *)jk_hist<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
+  GDF_TRY(allow_lds(jk_hist<8>, hist_lds));
+  GDF_TRY(allow_lds(jk_hist<4>, hist_lds));
+  GDF_TRY(allow_lds(jk_hist<0>, hist_lds));
   long long *d_mm = nullptr;
   if (decide_narrow)
     d_mm = reinterpret_cast<long long *>(fine_hist.as<uint32_t>() + nfine);
@@ -3878,50 +3815,25 @@ static gdf_error spec_append_finish(const PartGeom &g, SpecAppend *app, SideBufs
   return GDF_SUCCESS;
 }
 
-template <bool NARROW>
-static gdf_error run_probe(bool write, const char *name, size_t nunits, size_t lds, const ProbeArgs &a, const KeyTable &probe_t,
-                           const KeyTable &build_t) {
+// the general probe kernel: jk_probe<write, narrow, six- / ten-byte probe tuples>
+static gdf_error run_probe(bool narrow, bool write, const char *name, size_t nunits, size_t lds, const ProbeArgs &a,
+                           const KeyTable &probe_t, const KeyTable &build_t) {
   if (!nunits) return GDF_SUCCESS;
-  if constexpr (!NARROW) {
-    if (a.p6_fb) {                 // ten-byte probe tuples
-      if (write) {
-        HIP_TRY(hipFuncSetAttribute((const void *)jk_probe<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GDF_LAUNCH(name, (jk_probe<true, false, true>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, stream0(), a, probe_t, build_t);
-      } else {
-        HIP_TRY(hipFuncSetAttribute((const void *)jk_probe<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GDF_LAUNCH(name, (jk_probe<false, false, true>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, stream0(), a, probe_t, build_t);
-      }
-      HIP_CHECK_LAST();
-      return GDF_SUCCESS;
-    }
-  }
-  if constexpr (NARROW) {
-    if (a.p6_fb) {                 // six-byte probe tuples
-      if (write) {
-        HIP_TRY(hipFuncSetAttribute((const void *)jk_probe<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GDF_LAUNCH(name, (jk_probe<true, true, true>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, stream0(), a, probe_t, build_t);
-      } else {
-        HIP_TRY(hipFuncSetAttribute((const void *)jk_probe<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GDF_LAUNCH(name, (jk_probe<false, true, true>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, stream0(), a, probe_t, build_t);
-      }
-      HIP_CHECK_LAST();
-      return GDF_SUCCESS;
-    }
-  }
-  if (write) {
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_probe<true, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GDF_LAUNCH(name, (jk_probe<true, NARROW>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, stream0(), a, probe_t, build_t);
-  } else {
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_probe<false, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GDF_LAUNCH(name, (jk_probe<false, NARROW>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, stream0(), a, probe_t, build_t);
-  }
+  GDF_TRY(with_bools([&](auto W, auto N, auto P6) {
+    return launch_lds(name, jk_probe<W(), N(), P6()>, dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, a, probe_t, build_t);
+  }, write, narrow, a.p6_fb != 0));
   HIP_CHECK_LAST();
   return GDF_SUCCESS;
 }
-static gdf_error run_probe(bool narrow, bool write, const char *name, size_t nunits, size_t lds, const ProbeArgs &a,
-                           const KeyTable &probe_t, const KeyTable &build_t) {
-  return narrow ? run_probe<true>(write, name, nunits, lds, a, probe_t, build_t)
-                : run_probe<false>(write, name, nunits, lds, a, probe_t, build_t);
+
+// Table size of the lean kernels (jk_probe_fast / jk_count_fast / jk_probe_bp), written to fa->nslots; returns POW2.
+// The general kernel's H is the power of two >= the largest build partition: between 25 % and 50 % table load.
+// A cuckoo build above ~42 % runs into cycles often (measured at 1.25e8 build rows: 3814 tuples per partition in
+// 2 x 4096 slots), so the lean kernel then sizes its tables for 40 % and takes slots with a mulhi.
+static bool lean_table(uint32_t max_build, ProbeArgs *fa) {
+  const bool pow2 = (double)max_build <= 0.42 * 2.0 * (double)fa->nslots;
+  if (!pow2) fa->nslots = ((uint32_t)(max_build * 1.25) + 63) & ~63u;
+  return pow2;
 }
 
 // WRITE pass over all units.  PLAIN joins (see jk_probe_fast) run the lean kernel first and hand the units whose
@@ -3934,68 +3846,38 @@ static gdf_error run_write_pass(bool narrow, bool plain, size_t nunits, size_t l
   DevBuf todo;
   RMM_TRY(todo.alloc(sizeof(uint32_t) * nunits));
   a.unit_todo = todo.as<uint32_t>();
-  // The general kernel's H is the power of two >= the largest build partition: between 25 % and 50 % table load.
-  // A cuckoo build above ~42 % runs into cycles often (measured at 1.25e8 build rows: 3814 tuples per partition in
-  // 2 x 4096 slots), so the lean kernel then sizes its tables for 40 % and takes slots with a mulhi.
   ProbeArgs fa = a;
-  const bool pow2 = (double)max_build <= 0.42 * 2.0 * (double)a.nslots;
-  if (!pow2) fa.nslots = ((uint32_t)(max_build * 1.25) + 63) & ~63u;
+  const bool pow2 = lean_table(max_build, &fa);
   // (the lean kernels never chain: without the general kernel's next[] a WIDE image of C3's partitions is 73 KB instead of 86 -- TWO
   // workgroups per CU instead of one; round 6, the 12-byte tuples' probe pass had run at half occupancy since round 2)
   const size_t flds = probe_lds_bytes(narrow, a.cap, fa.nslots, false);
-#define JK_FAST_LAUNCH(...)                                                                                                      \
-  do {                                                                                                                           \
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_probe_fast<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds)); \
-    GDF_LAUNCH("jk_probe_write", (jk_probe_fast<__VA_ARGS__>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), flds, stream0(), fa); \
-  } while (0)
   const bool keep = a.keep_unmatched_probe != 0;
+  // jk_probe_fast<pow2, keep, NARROW, PMODE, P6>: the (NARROW, PMODE, P6) families that exist are chosen below
+  auto lean = [&](auto N, auto M, auto P6) {
+    return with_bools([&](auto P2, auto KP) {
+      return launch_lds("jk_probe_write", jk_probe_fast<P2(), KP(), N(), M(), P6()>, dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), flds, fa);
+    }, pow2, keep);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  constexpr std::integral_constant<int, 0> none{};
   if (narrow && a.bpay_mode && !keep) {        // the build relation's payload word rides in the LDS image (jk_probe_bp)
     const bool bw2 = a.bpay_mode == 4;
     const size_t blds = probe_bp_lds_bytes(a.cap, fa.nslots, bw2);
-#define JK_BP_LAUNCH(P2, PPAY, B2)                                                                                                \
-  do {                                                                                                                            \
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_probe_bp<P2, PPAY, B2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds)); \
-    GDF_LAUNCH("jk_probe_write", (jk_probe_bp<P2, PPAY, B2>), dim3((unsigned)nunits), dim3(JK_BP_THREADS), blds, stream0(), fa);  \
-  } while (0)
-#define JK_BP_PICK(P2)                                                                                                            \
-  do {                                                                                                                            \
-    if (a.pay_mode == 4 && bw2) JK_BP_LAUNCH(P2, 2, true); else if (a.pay_mode == 4) JK_BP_LAUNCH(P2, 2, false);                   \
-    else if (a.pay_mode && bw2) JK_BP_LAUNCH(P2, 1, true); else if (a.pay_mode) JK_BP_LAUNCH(P2, 1, false);                        \
-    else if (bw2) JK_BP_LAUNCH(P2, 0, true); else JK_BP_LAUNCH(P2, 0, false);                                                      \
-  } while (0)
-    if (pow2) JK_BP_PICK(true); else JK_BP_PICK(false);
-#undef JK_BP_PICK
-#undef JK_BP_LAUNCH
+    GDF_TRY(with_bools([&](auto P2, auto B2) {
+      return with_int<0, 1, 2>(pay_words(a.pay_mode), [&](auto PP) {
+        return launch_lds("jk_probe_write", jk_probe_bp<P2(), PP(), B2()>, dim3((unsigned)nunits), dim3(JK_BP_THREADS), blds, fa);
+      });
+    }, pow2, bw2));
   } else if (narrow && a.p6_fb) {      // six-byte probe tuples (never together with carried columns)
-    if (pow2 && keep) JK_FAST_LAUNCH(true, true, true, 0, true);
-    else if (pow2) JK_FAST_LAUNCH(true, false, true, 0, true);
-    else if (keep) JK_FAST_LAUNCH(false, true, true, 0, true);
-    else JK_FAST_LAUNCH(false, false, true, 0, true);
+    GDF_TRY(lean(yes, none, yes));
   } else if (narrow && a.pay_mode) {
-#define JK_FAST_PAY(M)                                                                                                             \
-  do {                                                                                                                             \
-    if (pow2 && keep) JK_FAST_LAUNCH(true, true, true, M); else if (pow2) JK_FAST_LAUNCH(true, false, true, M);                    \
-    else if (keep) JK_FAST_LAUNCH(false, true, true, M); else JK_FAST_LAUNCH(false, false, true, M);                                \
-  } while (0)
-    if (a.pay_mode == 1) JK_FAST_PAY(1); else if (a.pay_mode == 2) JK_FAST_PAY(2); else if (a.pay_mode == 3) JK_FAST_PAY(3); else JK_FAST_PAY(4);
-#undef JK_FAST_PAY
+    GDF_TRY(with_int<1, 2, 3, 4>(a.pay_mode, [&](auto M) { return lean(yes, M, no); }));
   } else if (narrow) {
-    if (pow2 && keep) JK_FAST_LAUNCH(true, true, true);
-    else if (pow2) JK_FAST_LAUNCH(true, false, true);
-    else if (keep) JK_FAST_LAUNCH(false, true, true);
-    else JK_FAST_LAUNCH(false, false, true);
-  } else if (a.p6_fb) {                // WIDE keys on ten-byte probe tuples
-    if (pow2 && keep) JK_FAST_LAUNCH(true, true, false, 0, true);
-    else if (pow2) JK_FAST_LAUNCH(true, false, false, 0, true);
-    else if (keep) JK_FAST_LAUNCH(false, true, false, 0, true);
-    else JK_FAST_LAUNCH(false, false, false, 0, true);
-  } else {
-    if (pow2 && keep) JK_FAST_LAUNCH(true, true, false);
-    else if (pow2) JK_FAST_LAUNCH(true, false, false);
-    else if (keep) JK_FAST_LAUNCH(false, true, false);
-    else JK_FAST_LAUNCH(false, false, false);
+    GDF_TRY(lean(yes, none, no));
+  } else {                             // WIDE keys, on ten-byte probe tuples or twelve-byte ones
+    GDF_TRY(with_bools([&](auto P6) { return lean(no, none, P6); }, a.p6_fb != 0));
   }
-#undef JK_FAST_LAUNCH
   HIP_CHECK_LAST();
   unsigned long long left = 0;
   HIP_TRY(read_back(&left, a.opt_state + 2, sizeof(left)));
@@ -4007,21 +3889,9 @@ static gdf_error run_write_pass(bool narrow, bool plain, size_t nunits, size_t l
 // both passes of a plain join whose build keys repeat (jk_probe_multi): NARROW tuples, no carried columns, no FULL-join marks
 static gdf_error run_multi_pass(bool write, size_t nunits, size_t lds, const ProbeArgs &a) {
   if (!nunits) return GDF_SUCCESS;
-  const bool keep = a.keep_unmatched_probe != 0, p6 = a.p6_fb != 0;
-  const char *name = write ? "jk_probe_write" : "jk_probe_count";
-#define JK_MM_LAUNCH(W, KP, SIX)                                                                                                   \
-  do {                                                                                                                            \
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_probe_multi<W, KP, SIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    GDF_LAUNCH(name, (jk_probe_multi<W, KP, SIX>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, stream0(), a);            \
-  } while (0)
-  if (write) {
-    if (keep && p6) JK_MM_LAUNCH(true, true, true); else if (keep) JK_MM_LAUNCH(true, true, false);
-    else if (p6) JK_MM_LAUNCH(true, false, true); else JK_MM_LAUNCH(true, false, false);
-  } else {
-    if (keep && p6) JK_MM_LAUNCH(false, true, true); else if (keep) JK_MM_LAUNCH(false, true, false);
-    else if (p6) JK_MM_LAUNCH(false, false, true); else JK_MM_LAUNCH(false, false, false);
-  }
-#undef JK_MM_LAUNCH
+  GDF_TRY(with_bools([&](auto W, auto KP, auto SIX) {
+    return launch_lds(write ? "jk_probe_write" : "jk_probe_count", jk_probe_multi<W(), KP(), SIX()>, dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), lds, a);
+  }, write, a.keep_unmatched_probe != 0, a.p6_fb != 0));
   HIP_CHECK_LAST();
   return GDF_SUCCESS;
 }
@@ -4037,29 +3907,11 @@ static gdf_error run_count_pass(bool narrow, bool plain, size_t nunits, size_t l
   RMM_TRY(todo.alloc(sizeof(uint32_t) * nunits));
   a.unit_todo = todo.as<uint32_t>();
   ProbeArgs fa = a;
-  const bool pow2 = (double)max_build <= 0.42 * 2.0 * (double)a.nslots;      // as run_write_pass
-  if (!pow2) fa.nslots = ((uint32_t)(max_build * 1.25) + 63) & ~63u;
+  const bool pow2 = lean_table(max_build, &fa);
   const size_t flds = probe_lds_bytes(narrow, a.cap, fa.nslots, false);
-#define JK_COUNT_LAUNCH(...)                                                                                                     \
-  do {                                                                                                                            \
-    HIP_TRY(hipFuncSetAttribute((const void *)jk_count_fast<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds)); \
-    GDF_LAUNCH("jk_probe_count", (jk_count_fast<__VA_ARGS__>), dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), flds, stream0(), fa); \
-  } while (0)
-  const bool keep = a.keep_unmatched_probe != 0;
-  if (narrow && a.p6_fb) {
-    if (pow2 && keep) JK_COUNT_LAUNCH(true, true, true, true); else if (pow2) JK_COUNT_LAUNCH(true, false, true, true);
-    else if (keep) JK_COUNT_LAUNCH(false, true, true, true); else JK_COUNT_LAUNCH(false, false, true, true);
-  } else if (narrow) {
-    if (pow2 && keep) JK_COUNT_LAUNCH(true, true, true); else if (pow2) JK_COUNT_LAUNCH(true, false, true);
-    else if (keep) JK_COUNT_LAUNCH(false, true, true); else JK_COUNT_LAUNCH(false, false, true);
-  } else if (a.p6_fb) {
-    if (pow2 && keep) JK_COUNT_LAUNCH(true, true, false, true); else if (pow2) JK_COUNT_LAUNCH(true, false, false, true);
-    else if (keep) JK_COUNT_LAUNCH(false, true, false, true); else JK_COUNT_LAUNCH(false, false, false, true);
-  } else {
-    if (pow2 && keep) JK_COUNT_LAUNCH(true, true, false); else if (pow2) JK_COUNT_LAUNCH(true, false, false);
-    else if (keep) JK_COUNT_LAUNCH(false, true, false); else JK_COUNT_LAUNCH(false, false, false);
-  }
-#undef JK_COUNT_LAUNCH
+  GDF_TRY(with_bools([&](auto P2, auto KP, auto N, auto P6) {
+    return launch_lds("jk_probe_count", jk_count_fast<P2(), KP(), N(), P6()>, dim3((unsigned)nunits), dim3(JK_PROBE_THREADS), flds, fa);
+  }, pow2, a.keep_unmatched_probe != 0, narrow, a.p6_fb != 0));
   HIP_CHECK_LAST();
   unsigned long long left = 0;
   HIP_TRY(read_back(&left, a.opt_state + 2, sizeof(left)));
@@ -4323,13 +4175,9 @@ static gdf_error probe_prepared(const KeyTable &probe_t, const KeyTable &build_t
     RMM_TRY(d_counts.alloc(sizeof(uint32_t) * ((size_t)nfine_p + 1)));
     HIP_TRY(hipMemsetAsync(d_counts.p, 0, sizeof(uint32_t) * ((size_t)nfine_p + 1), stream0()));
     const size_t lds = sizeof(uint32_t) * nfine_p;
-    if (probe_fast == 8) {
-      HIP_TRY(hipFuncSetAttribute((const void *)jk_sample_caps<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      GDF_LAUNCH("jk_sample_caps", jk_sample_caps<8>, dim3(256), dim3(1024), lds, stream0(), probe_t.col[0].data, probe_t.nrows, g.fb, d_counts.as<uint32_t>());
-    } else {
-      HIP_TRY(hipFuncSetAttribute((const void *)jk_sample_caps<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      GDF_LAUNCH("jk_sample_caps", jk_sample_caps<4>, dim3(256), dim3(1024), lds, stream0(), probe_t.col[0].data, probe_t.nrows, g.fb, d_counts.as<uint32_t>());
-    }
+    GDF_TRY(with_int<8, 4>(probe_fast, [&](auto F) {
+      return launch_lds("jk_sample_caps", jk_sample_caps<F()>, dim3(256), dim3(1024), lds, probe_t.col[0].data, probe_t.nrows, g.fb, d_counts.as<uint32_t>());
+    }));
     HIP_CHECK_LAST();
     SkewCaps caps;
     caps.fine.resize((size_t)nfine_p + 1);
@@ -5749,11 +5597,7 @@ static gdf_error fj_send(gdf_column *keys, int64_t lo, int64_t hi, int world, in
   const unsigned grid = (unsigned)(((uint64_t)a.n + a.chunk - 1) / a.chunk);
   const size_t lds = fj_scatter_lds();
   const bool pow2 = (world & (world - 1)) == 0 && (world > 1 || coarse_bits > 0) && !lab::path_on("GDF_FJ_NO_POW2");
-  auto launch = [&](auto kernel) -> gdf_error {
-    HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GDF_LAUNCH("fj_scatter", kernel, dim3(grid), dim3(FJ_THREADS), lds, stream0(), a);
-    return GDF_SUCCESS;
-  };
+  auto launch = [&](auto kernel) { return launch_lds("fj_scatter", kernel, dim3(grid), dim3(FJ_THREADS), lds, a); };
   if (kind == K_I64) GDF_TRY(pow2 ? launch(fj_scatter<long long, true>) : launch(fj_scatter<long long, false>));
   else GDF_TRY(pow2 ? launch(fj_scatter<int, true>) : launch(fj_scatter<int, false>));
   HIP_CHECK_LAST();

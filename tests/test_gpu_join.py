@@ -342,7 +342,12 @@ def test_carried_payload_matches_the_gather(gdf, how, payload, shape, kdt, force
 
 
 @pytest.mark.parametrize("how", ["inner", "left"])
-@pytest.mark.parametrize("cols", ["i64,i64+i64,i64", "i32,i64m,f32+i16,f64,i32", "i64m,i64+f64m", "i32,i32,i32+i64,i64,i64"])
+@pytest.mark.parametrize("cols", ["i64,i64+i64,i64", "i32,i64m,f32+i16,f64,i32", "i64m,i64+f64m", "i32,i32,i32+i64,i64,i64",
+                                  # one side without non-key columns, one and two payload words against two and one: every (probe words,
+                                  # build words) pair of the lean kernels, with the lean tables above 42 % load (30 000 build rows) ...
+                                  "i32+", "i32,i32+", "i64,i64+", "+i64", "+i64,i64", "i64,i64+i64",
+                                  # ... and below it (40 000 build rows: power-of-two tables)
+                                  "i64+@40k", "i32+@40k", "i32,i32+@40k", "i64,i64+@40k", "+i64@40k", "+i64,i64@40k", "i64+i64,i64@40k", "i64,i64+i64@40k"])
 def test_one_payload_word_is_carried_and_the_rest_gathered(gdf, how, cols, force_path):
     """Relations with SEVERAL non-key columns: one 64-bit word per side travels with the tuples -- the first
     unmasked 8-byte column, else the first two unmasked 4-byte ones -- and every other column (further ones, masked ones, 2-byte
@@ -350,14 +355,15 @@ def test_one_payload_word_is_carried_and_the_rest_gathered(gdf, how, cols, force
     joining.cu:375-479).  'm' marks a column with a validity mask."""
     import zlib
     rs = np.random.RandomState(zlib.crc32(cols.encode()) % 100000)
-    npr, nb = 300_000, 30_000
+    cols, _, size = cols.partition("@")
+    npr, nb = (400_000, 40_000) if size == "40k" else (300_000, 30_000)
     force_path("GDF_JK_SPEC_MIN", "1000")
     build = rs.permutation(nb + nb // 4)[:nb].astype(np.int64)
     probe = rs.randint(0, nb + nb // 4, size=npr).astype(np.int64)
 
     def make(spec, n):
         arrs, valids = [], []
-        for name in spec.split(","):
+        for name in filter(None, spec.split(",")):
             masked = name.endswith("m")
             dt = {"i64": np.int64, "f64": np.float64, "i32": np.int32, "f32": np.float32, "i16": np.int16}[name.rstrip("m")]
             arrs.append(rs.random_sample(n).astype(dt) if np.dtype(dt).kind == "f" else rs.randint(-30000, 30000, size=n).astype(dt))
@@ -388,7 +394,8 @@ def test_one_payload_word_is_carried_and_the_rest_gathered(gdf, how, cols, force
 
 
 @pytest.mark.parametrize("how", ["inner", "left"])
-@pytest.mark.parametrize("shape", ["all-hit", "half-hit", "80pct-hit", "dup-build-keys", "small-exact-layout", "skewed", "headline-geometry", "three-per-side"])
+@pytest.mark.parametrize("shape", ["all-hit", "half-hit", "80pct-hit", "dup-build-keys", "small-exact-layout", "skewed", "headline-geometry", "three-per-side",
+                                   "int32-keys"])
 def test_two_payload_words_per_side(gdf, how, shape, force_path):
     """Round 6: a relation with TWO unmasked 8-byte non-key columns carries both -- a 16-byte payload element
     through jk_scatter1_pay<.., 4> (6144-tuple tiles), jk_scatter2<.., 2> and the probe kernels (csrc/join.hip PayCarry mode 4) -- and an
@@ -412,6 +419,8 @@ def test_two_payload_words_per_side(gdf, how, shape, force_path):
     probe = rs.randint(0, space if shape != "dup-build-keys" else nb // 4, size=npr).astype(np.int64)
     if shape == "skewed":
         probe[rs.randint(0, npr, size=npr // 8)] = build[0]
+    if shape == "int32-keys":                      # (jk_scatter1_pay reads a 4-byte key column next to the 16-byte payload element)
+        build, probe = build.astype(np.int32), probe.astype(np.int32)
     ncols = 3 if shape == "three-per-side" else 2
     pays = [rs.randint(-2**62, 2**62, size=npr).astype(np.int64), rs.random_sample(npr)] + ([rs.randint(0, 99, size=npr).astype(np.int64)] if ncols == 3 else [])
     bpays = [rs.random_sample(nb), rs.randint(-2**62, 2**62, size=nb).astype(np.int64)] + ([rs.random_sample(nb)] if ncols == 3 else [])
@@ -869,7 +878,7 @@ def test_masked_single_key_column_takes_the_paired_reads(gdf, how, dtype, masks,
 
 @pytest.mark.parametrize("how", ["inner", "left"])
 @pytest.mark.parametrize("keys", ["int64-from-zero", "int64-offset", "int64-straddling-2^32", "int32", "two-int16-columns", "build-keys-twice",
-                                  "probe-third-on-one-key"])
+                                  "probe-third-on-one-key", "lean-tables-above-42pct-load"])
 @pytest.mark.parametrize("hit", [1.0, 0.7, 0.2])
 def test_six_byte_level2_tuples(gdf, how, keys, hit, force_path):
     """With 2^15 fine partitions the level-2 output and the probe input are SIX-byte tuples -- 17 remaining bits of the (bijective)
@@ -881,6 +890,8 @@ def test_six_byte_level2_tuples(gdf, how, keys, hit, force_path):
     key (the exact layout's level 2 writes six-byte tuples too; GDF_JK_NO_P6_EXACT: eight-byte ones there), every output-sizing path."""
     rs = np.random.RandomState(int(hit * 10) + len(keys))
     nb, npr = 60_000, 900_000
+    if keys == "lean-tables-above-42pct-load":      # ~35 build rows per partition, the largest of 2^15 between 54 and 64: more than 42 % of two
+        nb = 1_150_000                               # 64-slot tables, so the lean kernels size their tables for 40 % (not a power of two)
     force_path("GDF_JK_FORCE_FB", "15")
     force_path("GDF_JK_SPEC_MIN", "1000")
     space = int(nb / hit)
@@ -901,6 +912,9 @@ def test_six_byte_level2_tuples(gdf, how, keys, hit, force_path):
     else:
         build, probe = [bk], [pk]
     n1 = _check(gdf, probe, build, how)
+    if keys == "lean-tables-above-42pct-load":      # ... in the count + write passes of an INNER join too, on six- and on eight-byte tuples
+        force_path("GDF_JK_NO_SPARSE_OPT")
+        assert _check(gdf, probe, build, how) == n1
     force_path("GDF_JK_NO_P6_EXACT")
     assert _check(gdf, probe, build, how) == n1
     force_path("GDF_JK_NO_P6")
@@ -908,7 +922,7 @@ def test_six_byte_level2_tuples(gdf, how, keys, hit, force_path):
 
 
 @pytest.mark.parametrize("how", ["inner", "left"])
-@pytest.mark.parametrize("keys", ["int64", "int64-offset", "int32", "masked", "build-keys-twice", "nine-million-rows", "probe-third-on-one-key"])
+@pytest.mark.parametrize("keys", ["int64", "int64-offset", "int32", "masked", "masked-int32", "build-keys-twice", "nine-million-rows", "probe-third-on-one-key"])
 def test_six_byte_level1_tuples(gdf, how, keys, force_path):
     """The probe side's LEVEL-1 tuples are six bytes too on the main path (csrc/join.hip L6): 24 hash bits (the
     coarse partition is the tuple's place) + 24 explicit row bits (bits 17..22 of the row number are the tuple's REGION: level 1
@@ -933,9 +947,9 @@ def test_six_byte_level1_tuples(gdf, how, keys, force_path):
     if keys == "int64-offset":
         bk, pk = bk + (5 << 34) + 999, pk + (5 << 34) + 999
     lv = rv = None
-    if keys == "masked":
+    if keys in ("masked", "masked-int32"):
         lv, rv = [rs.rand(npr) > 0.1], [rs.rand(nb) > 0.05]
-    if keys == "int32":
+    if keys in ("int32", "masked-int32"):
         bk, pk = bk.astype(np.int32), pk.astype(np.int32)
     n1 = _check(gdf, [pk], [bk], how, lv, rv)
     force_path("GDF_JK_NO_L6")
@@ -944,7 +958,7 @@ def test_six_byte_level1_tuples(gdf, how, keys, force_path):
 
 @pytest.mark.parametrize("how", ["inner", "left"])
 @pytest.mark.parametrize("keys", ["spread-over-2^62", "negative-and-positive", "two-dense-clusters", "fold-colliders", "float64", "masked",
-                                  "build-keys-twice", "nine-million-rows", "probe-third-on-one-key", "half-hit"])
+                                  "build-keys-twice", "nine-million-rows", "probe-third-on-one-key", "half-hit", "half-hit-lean-tables-above-42pct-load"])
 def test_ten_byte_tuples_for_wide_keys(gdf, how, keys, force_path):
     """int64 keys that do not fit 32 bits travel as TEN-byte tuples on the main path (csrc/join.hip p10_key): the
     six-byte tuple of the NARROW path -- remainder of the partition hash + row -- plus the raw key's HIGH WORD in a parallel array.
@@ -956,6 +970,9 @@ def test_ten_byte_tuples_for_wide_keys(gdf, how, keys, force_path):
     word only -- in the build relation, plus probe keys of the same families that are NOT in the build relation and must not match."""
     rs = np.random.RandomState(len(keys) + 3)
     nb, npr = 60_000, (9_000_000 if keys == "nine-million-rows" else 900_000)
+    if keys == "half-hit-lean-tables-above-42pct-load":      # ~35 build rows per partition, the largest between 54 and 64 (see the six-byte test);
+        nb = 1_150_000                                        # count + write passes of the INNER join as well (GDF_JK_NO_SPARSE_OPT)
+        force_path("GDF_JK_NO_SPARSE_OPT")
     force_path("GDF_JK_FORCE_FB", "15")
     force_path("GDF_JK_SPEC_MIN", "1000")
     force_path("GDF_JK_FORCE_L6")
@@ -971,7 +988,7 @@ def test_ten_byte_tuples_for_wide_keys(gdf, how, keys, force_path):
         bk = np.unique(rs.randint(0, 2**62, size=nb, dtype=np.int64))
         rs.shuffle(bk)
         pk = bk[rs.randint(0, len(bk), size=npr)]
-        if keys == "half-hit":
+        if keys.startswith("half-hit"):
             miss = rs.rand(npr) < 0.5
             pk[miss] = rs.randint(0, 2**62, size=int(miss.sum()), dtype=np.int64)
     if keys == "fold-colliders":
@@ -1191,7 +1208,7 @@ def test_skewed_probe_side_overflows_the_deferred_layout(gdf, how):
 
 
 @pytest.mark.parametrize("how", ["inner", "left"])
-@pytest.mark.parametrize("skew", ["zipf", "tenth-on-one-key", "half-on-eight-keys"])
+@pytest.mark.parametrize("skew", ["zipf", "tenth-on-one-key", "half-on-eight-keys", "tenth-on-one-key-int32"])
 def test_skewed_probe_side_keeps_the_histogram_free_layout(gdf, how, skew, force_path):
     """Skewed probe keys no longer force the exact layout's histogram pass over the probe relation: a 2^22-row
     sample of the probe column sizes every level-1 region and every fine partition individually (csrc/join.hip SkewCaps) and the
@@ -1214,7 +1231,7 @@ def test_skewed_probe_side_keeps_the_histogram_free_layout(gdf, how, skew, force
         probe[torch.rand(npr, generator=g, device="cuda") < 0.05] = nb + nb // 8 + 5       # a twentieth of the rows miss
     else:
         probe = torch.randint(0, nb + nb // 8, (npr,), generator=g, device="cuda")
-        if skew == "tenth-on-one-key":
+        if skew.startswith("tenth-on-one-key"):
             probe[torch.rand(npr, generator=g, device="cuda") < 0.1] = int(build[3])
         else:
             hot = build[:8]
@@ -1223,6 +1240,8 @@ def test_skewed_probe_side_keeps_the_histogram_free_layout(gdf, how, skew, force
     present = torch.zeros(nb + nb // 8 + 6, dtype=torch.bool, device="cuda")
     present[build] = True
     expected = int(present[probe].sum())
+    if skew.endswith("int32"):                      # (jk_sample_caps reads a 4-byte key column)
+        build, probe = build.int(), probe.int()
     lonely = npr - expected if how == "left" else 0
     lib = gdf._binding._gdf_cdll
 
