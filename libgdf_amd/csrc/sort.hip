@@ -349,8 +349,14 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter(const K *__restrict__ k
 // Sorts n pairs by the key bits set in `varying` (bits on which all keys agree need no
 // pass).  The pairs ping-pong between (kin, vin) and (kout, vout); on return kin / vin
 // point at the sorted data.  The varying bits [lo, hi) are covered by ceil(span / 9)
-// windows of at most 9 bits (8-bit digits for wide keys, 9 when that saves a pass:
-// 25 bits sort in 3 passes); windows may overlap upward, which a stable LSD sort tolerates.
+// windows of 8 or 9 bits (8-bit digits for wide keys, 9 when that saves a pass: 25 bits
+// sort in 3 passes).  A window is always 8 or 9 bits wide, so windows overlap upward and
+// the last one may reach past hi: it sorts on whatever the keys hold there.
+// PRECONDITION: all keys agree on every bit above the highest set bit of `varying` (at or
+// above hi) -- true when `varying` is the real difference mask of the keys, or that mask
+// with LOW bits cleared (hybrid_sort_pairs' top bits, the group-by's partition bits).
+// A caller that wants bits ABOVE a range ignored clears them in the keys (rsw_image); bits
+// below lo may differ freely, no window reads them.
 template <class K, class V>
 gdf_error radix_sort_pairs(K *&kin, K *&kout, V *&vin, V *&vout, uint32_t n, uint64_t varying) {
   if (varying == 0 || n < 2) return GDF_SUCCESS;
@@ -1046,9 +1052,16 @@ gdf_error group_by_sort(int ncols, gdf_column **cols, gdf_column *col_agg, gdf_c
 // over cub::DeviceRadixSort / DeviceSegmentedRadixSort with a plan object that owns the back buffers).  Here the
 // plan only records its parameters: the keys' order-preserving images (complemented for a descending sort) and
 // their row numbers go through the LSD radix sort above, then keys and values are gathered through the
-// permutation.  Stable like CUB's (equal keys keep their input order, ascending and descending alike);
-// begin_bit / end_bit restrict the sort to those bits of the image.  -0.0 and +0.0 compare equal and NaN orders
-// after +inf (numpy's order; CUB orders by the raw bit pattern there).
+// permutation.  Stable like CUB's (equal keys keep their input order, ascending and descending alike).  -0.0 and
+// +0.0 compare equal and NaN orders after +inf (numpy's order; CUB orders by the raw bit pattern there).
+//
+// begin_bit / end_bit select bits [begin_bit, end_bit) of the IMAGE, in the key's width W: for an integer its two's
+// complement with the sign bit flipped; for a float the total-order image with -0.0 canonicalised to +0.0 and every NaN
+// to all ones (so a partial range sees neither the sign of a zero nor a NaN's payload); complemented within W for a
+// descending sort.  Rows are ordered by those bits alone and rows that agree on them keep their input order: no bit
+// outside the range has any influence (rsw_image clears them before the sort).  Both bounds are clamped to W
+// (end_bit = W + 8 means W); an empty range after clamping -- begin_bit == end_bit, end_bit < begin_bit, begin_bit >= W
+// -- leaves both columns as they are.  The key and value OUTPUT are always the caller's original elements, gathered.
 // ---------------------------------------------------------------------------
 struct RadixPlan {
   size_t num_items;
@@ -1057,7 +1070,9 @@ struct RadixPlan {
   size_t sizeof_key, sizeof_val;
 };
 
-__device__ __forceinline__ uint64_t rsw_image(const void *key, int kind, int descending, const uint32_t *region,
+// `range`: the image bits the caller sorts on.  Every other bit is cleared HERE, so that the varying mask radix_sort_pairs gets
+// names in-range bits only and its windows, which may reach past the highest of them, find nothing that differs there
+__device__ __forceinline__ uint64_t rsw_image(const void *key, int kind, int descending, uint64_t range, const uint32_t *region,
                                               const uint8_t *region_sorted, uint32_t i) {
   const int bits = (kind == K_I8 ? 8 : (kind == K_I16 ? 16 : ((kind == K_I32 || kind == K_F32) ? 32 : 64)));
   const uint64_t mask = bits >= 64 ? ~0ULL : ((1ULL << bits) - 1ULL);
@@ -1065,16 +1080,17 @@ __device__ __forceinline__ uint64_t rsw_image(const void *key, int kind, int des
   if (kind == K_F32 || kind == K_F64) k = ordered_float_bits(key, kind, i);
   else k = ((uint64_t)load_signed_kind(key, kind, i) ^ (1ULL << (bits - 1))) & mask;
   if (descending) k = ~k & mask;
+  k &= range;
   if (region && !region_sorted[region[i]]) k = 0;          // rows outside every segment keep their order
   return k;
 }
-__global__ __launch_bounds__(256) void rsw_images(const void *key, int kind, int descending, const uint32_t *__restrict__ region,
+__global__ __launch_bounds__(256) void rsw_images(const void *key, int kind, int descending, uint64_t range, const uint32_t *__restrict__ region,
                                                   const uint8_t *__restrict__ region_sorted, uint64_t *__restrict__ img,
                                                   uint32_t *__restrict__ row, uint32_t n, unsigned long long *__restrict__ varying) {
-  const uint64_t k0 = rsw_image(key, kind, descending, region, region_sorted, 0);
+  const uint64_t k0 = rsw_image(key, kind, descending, range, region, region_sorted, 0);
   uint64_t diff = 0;
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const uint64_t k = rsw_image(key, kind, descending, region, region_sorted, i);
+    const uint64_t k = rsw_image(key, kind, descending, range, region, region_sorted, i);
     img[i] = k;
     row[i] = i;
     diff |= k ^ k0;
@@ -1140,7 +1156,8 @@ static gdf_error radixsort_api(const RadixPlan *plan, gdf_column *keycol, gdf_co
       HIP_TRY(read_back(he.data(), d_end, sizeof(unsigned) * nseg));
     }
     std::vector<uint32_t> bounds;
-    for (int s = 0; s < nseg; ++s) { bounds.push_back(hb[s]); bounds.push_back(he[s]); }
+    for (int s = 0; s < nseg; ++s)
+      if (he[s] > hb[s]) { bounds.push_back(hb[s]); bounds.push_back(he[s]); }     // an empty segment sorts nothing and splits nothing
     std::sort(bounds.begin(), bounds.end());
     bounds.erase(std::unique(bounds.begin(), bounds.end()), bounds.end());
     nbounds = (uint32_t)bounds.size();
@@ -1169,10 +1186,10 @@ static gdf_error radixsort_api(const RadixPlan *plan, gdf_column *keycol, gdf_co
   uint32_t *vin = va.as<uint32_t>(), *vout = vb.as<uint32_t>();
   const int grid = stream_grid(n, 1024);
   GDF_LAUNCH("rsw_images", rsw_images, dim3(grid), dim3(256), 0, stream0(), (const void *)keycol->data, (int)kind, plan->descending,
-             (const uint32_t *)region.as<uint32_t>(), (const uint8_t *)rflags.as<uint8_t>(), kin, vin, n, vary.as<unsigned long long>());
+             range, (const uint32_t *)region.as<uint32_t>(), (const uint8_t *)rflags.as<uint8_t>(), kin, vin, n, vary.as<unsigned long long>());
   unsigned long long varying = 0;
   HIP_TRY(read_back(&varying, vary.p, sizeof(varying)));
-  GDF_TRY((radix_sort_pairs<uint64_t, uint32_t>(kin, kout, vin, vout, n, varying & range)));
+  GDF_TRY((radix_sort_pairs<uint64_t, uint32_t>(kin, kout, vin, vout, n, varying)));      // in-range bits only: rsw_image masked the images
   if (nseg >= 0 && nbounds) {
     // second, stable sort on the region number puts every row back into its own region
     hipLaunchKernelGGL(rsw_region_keys, dim3(grid), dim3(256), 0, stream0(), (const uint32_t *)region.as<uint32_t>(), (const uint32_t *)vin, kin, n);
@@ -1205,7 +1222,7 @@ gdf_error sort_column_inplace(void *data, ElemKind kind, uint32_t n) {
   uint64_t *kin = ka.as<uint64_t>(), *kout = kb.as<uint64_t>();
   uint32_t *vin = va.as<uint32_t>(), *vout = vb.as<uint32_t>();
   const int grid = stream_grid(n, 1024);
-  GDF_LAUNCH("rsw_images", rsw_images, dim3(grid), dim3(256), 0, stream0(), (const void *)data, (int)kind, 0, (const uint32_t *)nullptr,
+  GDF_LAUNCH("rsw_images", rsw_images, dim3(grid), dim3(256), 0, stream0(), (const void *)data, (int)kind, 0, ~0ULL, (const uint32_t *)nullptr,
              (const uint8_t *)nullptr, kin, vin, n, vary.as<unsigned long long>());
   unsigned long long varying = 0;
   HIP_TRY(read_back(&varying, vary.p, sizeof(varying)));

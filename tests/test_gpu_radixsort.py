@@ -8,24 +8,10 @@ from itertools import product
 import numpy as np
 import pytest
 
+from radixsort_common import api as _api
 from util import gen_rand
 
 pytestmark = pytest.mark.gpu
-
-
-def _api():
-    from libgdf_amd._binding import _gdf_cdll as lib
-    lib.gdf_radixsort_plan.restype = C.c_void_p
-    lib.gdf_radixsort_plan.argtypes = [C.c_size_t, C.c_int, C.c_uint, C.c_uint]
-    lib.gdf_segmented_radixsort_plan.restype = C.c_void_p
-    lib.gdf_segmented_radixsort_plan.argtypes = [C.c_size_t, C.c_int, C.c_uint, C.c_uint]
-    for n in ("gdf_radixsort_plan_setup", "gdf_segmented_radixsort_plan_setup"):
-        getattr(lib, n).argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
-    for n in ("gdf_radixsort_plan_free", "gdf_segmented_radixsort_plan_free"):
-        getattr(lib, n).argtypes = [C.c_void_p]
-    lib.gdf_radixsort_generic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.gdf_segmented_radixsort_generic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
-    return lib
 
 
 def _expected(key, descending):
