@@ -13,6 +13,11 @@ extern "C" {
 gdf_error gdf_amd_debug_force(const char *name, const char *value);
 /* what libgdf.so asks: the value forced for `name`, or NULL */
 const char *gdf_amd_testhook_forced(const char *name);
+/* the note channel, the other direction: libgdf.so reports which route a call took (a second weak reference, null without this
+ * library; csrc/lab.h note()), the last value per name is kept.  Forcing a path does not clear notes. */
+void gdf_amd_testhook_note(const char *name, long long value);
+/* the last value noted under `name` -> *value; GDF_INVALID_API_CALL when nothing was noted under it.  value NULL clears every note. */
+gdf_error gdf_amd_debug_noted(const char *name, long long *value);
 #ifdef __cplusplus
 }
 #endif

@@ -293,7 +293,7 @@ def _check_rmm(rc, fname):
 
 
 class _GdfWrapper(_Wrapper):
-    """libgdf.so, plus the one name that lives in the test-hook library when a test process loaded it"""
+    """libgdf.so, plus the two names that live in the test-hook library when a test process loaded it"""
 
     def __getattr__(self, name):
         if name == "gdf_amd_debug_force":
@@ -303,6 +303,14 @@ class _GdfWrapper(_Wrapper):
             fn = _hook_cdll.gdf_amd_debug_force
             fn.restype = C.c_int
             fn.argtypes = [C.c_char_p, C.c_char_p]
+            return fn
+        if name == "gdf_amd_debug_noted":
+            if _hook_cdll is None:
+                raise AttributeError("gdf_amd_debug_noted lives in libgdf_testhook.so (test infrastructure): set LIBGDF_AMD_TESTHOOK=1 "
+                                     "before importing libgdf_amd")
+            fn = _hook_cdll.gdf_amd_debug_noted          # (unchecked: an unknown name is an answer, not an exception)
+            fn.restype = C.c_int
+            fn.argtypes = [C.c_char_p, C.POINTER(C.c_longlong)]
             return fn
         return super().__getattr__(name)
 

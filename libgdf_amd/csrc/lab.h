@@ -20,5 +20,9 @@ static inline const char *path(const char *name) { return forced(name); }
 static inline bool path_on(const char *name) { return path(name) != nullptr; }
 static inline long long path_int(const char *name, long long dflt) { const char *v = path(name); return v ? atoll(v) : dflt; }
 
+// plumbing.cpp: tell the test-hook library which route a call took (read back by gdf_amd_debug_noted).  Does nothing -- one pointer
+// test -- in every process that has not loaded libgdf_testhook.so; the library never reads a note.
+void note(const char *name, long long value);
+
 }  // namespace lab
 }  // namespace gdf_amd

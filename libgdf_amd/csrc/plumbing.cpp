@@ -18,6 +18,7 @@
 
 // (csrc/testhook.cpp; weak: absent from every process that has not loaded libgdf_testhook.so in front of this library)
 extern "C" __attribute__((weak, visibility("default"))) const char *gdf_amd_testhook_forced(const char *name);
+extern "C" __attribute__((weak, visibility("default"))) void gdf_amd_testhook_note(const char *name, long long value);
 
 namespace gdf_amd {
 
@@ -153,6 +154,7 @@ PlaceRound::~PlaceRound() {
 // load the hook library first.
 namespace lab {
 const char *forced(const char *name) { return gdf_amd_testhook_forced ? gdf_amd_testhook_forced(name) : nullptr; }
+void note(const char *name, long long value) { if (gdf_amd_testhook_note) gdf_amd_testhook_note(name, value); }
 }  // namespace lab
 
 }  // namespace gdf_amd

@@ -336,6 +336,9 @@ static gdf_error radix_select(const gdf_column *col, uint32_t k, bool one, uint6
   HIP_CHECK_LAST();
   QtCtl out;
   HIP_TRY(read_back(&out, &st->c, sizeof(out)));      // (synchronises the stream: the scratch can go)
+  lab::note("qt.column_passes", out.column_passes);   // (the route the search took, for the tests; a no-op without the hook library)
+  lab::note("qt.src", out.src);
+  lab::note("qt.allow_compact", out.allow_compact);
   if (!out.done || (!one && out.y1_state != Y1_KNOWN)) return GDF_CUDA_ERROR;
   *key0 = out.prefix;
   *key1 = one ? out.prefix : out.y1;

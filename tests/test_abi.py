@@ -305,6 +305,9 @@ def test_shipped_library_reads_no_environment(libs, hook):
     assert "debug_force" not in exported and "testhook" not in exported
     und = subprocess.check_output(["nm", "-D", "--undefined-only", os.path.join(LIBDIR, "libgdf.so")]).decode()
     assert any(l.split()[:1] == ["w"] and "gdf_amd_testhook_forced" in l for l in und.splitlines()), "the lookup must be a WEAK reference"
+    # the note channel runs the other way through a second weak reference, and libgdf.so exports neither end of it
+    assert any(l.split()[:1] == ["w"] and "gdf_amd_testhook_note" in l for l in und.splitlines()), "the note sink must be a WEAK reference"
+    assert not any(word in exported for word in ("testhook", "debug_force", "debug_noted"))
     assert hook.gdf_amd_debug_force(b"GDF_JK_NO_SPEC", b"1") == 0
     assert hook.gdf_amd_testhook_forced(b"GDF_JK_NO_SPEC") == b"1"
     assert hook.gdf_amd_debug_force(b"GDF_JK_NO_SPEC", None) == 0

@@ -47,8 +47,12 @@ def _check(op, got, want, values, valid=None):
     scale = float(np.sum(np.abs(v.astype(np.float64)) ** (2 if op == "sum_squared" else 1))) + 1.0
     if op == "product":              # accumulated in the input type, in another order than numpy's: relative error ~ n * eps
         tol = (1e-3 if dt == np.float32 else 1e-10) * (abs(float(want)) + 1e-30)
-    else:                            # f32 sums accumulate in f64 and round once
-        tol = (1e-6 if dt == np.float32 else 1e-12) * scale
+    elif dt == np.float32:
+        # the kernel accumulates in f64 and rounds once, as the reference value does: both f64 sums are within n * 2^-53 * scale of
+        # the true sum, so within n * 2^-52 * scale of each other, and each rounding to f32 adds half an ulp of the result
+        tol = float(np.spacing(np.float32(abs(float(want))))) + len(v) * 2.0 ** -52 * (scale - 1.0)
+    else:
+        tol = 1e-12 * scale
     assert abs(float(got) - float(want)) <= tol, (op, got, want)
 
 
