@@ -255,8 +255,11 @@ def group_by_sort(op, keys, values, out_dtype=None, distinct=False):
                 agg = (sums / c).astype(T)
             else:                                    # C++ integer division truncates toward zero
                 si, ci = sums.astype(np.int64), c.astype(np.int64)
-                q = np.where(ci != 0, np.abs(si) // np.maximum(np.abs(ci), 1), 0) * np.sign(si) * np.sign(ci)
-                agg = q.astype(T)
+                # (floor division, then one step back toward zero where it rounded away from it: np.abs would overflow on INT64_MIN)
+                cz = np.where(ci != 0, ci, 1)
+                q = si // cz
+                q = q + ((si - q * cz != 0) & ((si < 0) != (cz < 0)))
+                agg = np.where(ci != 0, q, 0).astype(T)
         else:
             raise ValueError(op)
     return out_keys, agg, idx

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+from groupby_values import check_masked as _check_masked, kernels_of as _kernels_of, zipf as _zipf
 from oracle import oracle
 from util import gen_rand, sort_groups
 
@@ -254,28 +255,6 @@ def test_all_valid_masks_change_nothing(gdf):
 
 
 # ---- validity masks (BASELINE config C5; beyond the reference, which rejects every mask) ------------------------
-def _check_masked(gdf, op, keys, vals, key_valids, val_valid, out_dtype=None, sort_result=False):
-    from libgdf_amd.columns import column_from_numpy, get_dtype
-    kc = [column_from_numpy(k, v) for k, v in zip(keys, key_valids)]
-    vc = column_from_numpy(vals, val_valid)
-    od = None if out_dtype is None else get_dtype(out_dtype)
-    gk, ga, gok = gdf.api.group_by(op, kc, vc, out_dtype=od, sort_result=sort_result, with_masks=True)
-    gk, ga, gok = [x.cpu().numpy() for x in gk], ga.cpu().numpy(), gok.numpy()
-    ek, ea, eok = oracle.group_by_masked(op, keys, vals, key_valids, val_valid, out_dtype)
-    if not (sort_result or op == "avg"):
-        order = np.lexsort(tuple(reversed(gk)))
-        gk, ga, gok = [k[order] for k in gk], ga[order], gok[order]
-    assert len(ga) == len(ea)
-    for g, e in zip(gk, ek):
-        np.testing.assert_array_equal(g, e)
-    np.testing.assert_array_equal(gok, eok)
-    assert (ga[~gok] == 0).all()
-    if op in ("sum", "avg") and np.asarray(vals).dtype.kind == "f":
-        np.testing.assert_allclose(ga[gok].astype(np.float64), ea[eok].astype(np.float64), rtol=1e-6, atol=1e-9)
-    else:
-        np.testing.assert_array_equal(ga[gok], ea[eok])
-
-
 @pytest.mark.parametrize("op", OPS)
 @pytest.mark.parametrize("val_dtype", [np.int32, np.int64, np.float32, np.float64], ids=lambda d: np.dtype(d).name)
 def test_masked_values_and_keys(gdf, op, val_dtype):
@@ -514,7 +493,8 @@ def test_fused_partition_pass_static_signatures(gdf, key_dtypes, val_dtype, op, 
     """>= 2^20 rows and more groups than one set of LDS accumulators: the fused partition pass, whose count / scatter kernels
     are instantiated per (key kinds, value mask) for one or two 4- / 8-byte integer key columns with an 8-byte value column
     (COUNT and every other shape keep the kernels with the type switches; GDF_GBP_DYNAMIC=1 forces those: same answers).
-    Without masks, with a value mask (SUM / MIN: no validity bit in the key; AVG: with it), with null key elements."""
+    Without masks, with a value mask (every masked operator but COUNT carries a validity bit in the key: gb_path_sorted's vbit), with null
+    key elements."""
     n = (1 << 20) + 4321
     rs = np.random.RandomState(11)
     first = rs.randint(-150_000, 150_000, size=n).astype(key_dtypes[0]) if len(key_dtypes) == 1 else \
@@ -533,23 +513,6 @@ def test_fused_partition_pass_static_signatures(gdf, key_dtypes, val_dtype, op, 
 
 
 # ---- hot key window: pre-aggregated in the fused scatter kernel's LDS (csrc/groupby.hip GbHot, gbp_scatter_static<..., HOT>) ----
-def _kernels_of(gdf, call):
-    """names of the kernels one library call launched (the exported profile hooks of include/gdf/gdf_amd_ext.h)"""
-    from bench import read_profile
-    lib = gdf._binding._gdf_cdll
-    lib.gdf_amd_profile_reset(); lib.gdf_amd_profile_enable(1)
-    try:
-        call()
-    finally:
-        lib.gdf_amd_profile_enable(0)
-    return set(read_profile(gdf))
-
-
-def _zipf(rs, n, values):
-    u = rs.random_sample(n)
-    return np.clip(np.exp(u * np.log(values + 1.0)).astype(np.int64) - 1, 0, values - 1)      # p(rank) ~ 1 / rank, rank = value
-
-
 @pytest.mark.parametrize("op,val_dtype,masked", [("avg", np.float64, True), ("sum", np.int64, False), ("sum", np.float64, True),
                                                  ("min", np.float64, True), ("max", np.int64, False)],
                          ids=["avg-f64-masked", "sum-i64", "sum-f64-masked", "min-f64-masked", "max-i64"])
