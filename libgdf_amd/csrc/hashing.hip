@@ -34,6 +34,26 @@ constexpr int HP_MAX_CHUNKS = 1024;
 constexpr int HP_MAX_LDS_PARTS = 16384;     // 64 KiB of LDS counters
 constexpr int HP_MAX_PAYLOAD_COLS = 32;     // columns moved per scatter launch
 
+// The route a gdf_hash_partition call took, noted for the tests (lab::note "hp.route").  Next to it: "hp.fastw" (0 / 4 / 8),
+// "hp.murmur" (0 / 1), "hp.nchunks", "hp.map_launches" (part_apply_map_kernel launches) and, on the two-level route, "hp.kshift" and
+// "hp.pieces".  A no-op without the test-hook library.
+enum HpRoute { HP_ROUTE_DIRECT_GENERIC = 0, HP_ROUTE_DIRECT_FAST = 1, HP_ROUTE_TILE = 2, HP_ROUTE_PAIRS = 3, HP_ROUTE_COLS8 = 4, HP_ROUTE_TWO_LEVEL = 5 };
+
+// at most this many chunks per call: HP_MAX_CHUNKS, or what the tests' size selector GDF_HP_MAX_CHUNKS says (like GDF_HP_PIECE: a few hundred
+// thousand rows then give chunks of several tiles), clamped to [1, 1024]
+static inline int64_t hp_max_chunks() {
+  const long long v = lab::path_int("GDF_HP_MAX_CHUNKS", HP_MAX_CHUNKS);
+  return v < 1 ? 1 : v > HP_MAX_CHUNKS ? HP_MAX_CHUNKS : v;
+}
+
+static inline void hp_note(int route, int fastw, bool murmur, int nchunks, int map_launches) {
+  lab::note("hp.route", route);
+  lab::note("hp.fastw", fastw);
+  lab::note("hp.murmur", murmur ? 1 : 0);
+  lab::note("hp.nchunks", nchunks);
+  lab::note("hp.map_launches", map_launches);
+}
+
 template <bool MURMUR>
 __global__ __launch_bounds__(HP_THREADS) void hash_rows_kernel(KeyTable t, uint32_t *__restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * HP_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * HP_THREADS)
@@ -1131,7 +1151,8 @@ static gdf_error hash_partition_two_level(int ncols, gdf_column *input[], const 
   // ---- level A.  Its histogram pass counts FULL partition ids per chunk (PartLevel mode 3): summed over a super-partition's K
   // partitions they are level A's own histogram, and summed over the chunks a level-B piece comes from they are level B's -- level B
   // needs no histogram pass, and nothing is read back between the levels ----
-  int64_t chunk = (n + HP_MAX_CHUNKS - 1) / HP_MAX_CHUNKS;
+  const int64_t max_chunks = hp_max_chunks();
+  int64_t chunk = (n + max_chunks - 1) / max_chunks;
   chunk = ((chunk + HP_THREADS * 8 - 1) / (HP_THREADS * 8)) * (HP_THREADS * 8);
   const int nchunks = (int)((n + chunk - 1) / chunk);
   const int grid = nchunks < NUM_CU * 4 ? nchunks : NUM_CU * 4;
@@ -1204,6 +1225,9 @@ static gdf_error hash_partition_two_level(int ncols, gdf_column *input[], const 
   HIP_CHECK_LAST();
   HIP_TRY(hipMemcpyAsync(partition_offsets, d_starts.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream0()));
   HIP_TRY(hipStreamSynchronize(stream0()));
+  hp_note(HP_ROUTE_TWO_LEVEL, fastw, murmur, nchunks, 0);
+  lab::note("hp.kshift", kshift);
+  lab::note("hp.pieces", (long long)M);
   return GDF_SUCCESS;
 }
 
@@ -1464,7 +1488,8 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
     if (!declined) return e;           // (declined: no room for the temporary table -- the one-level pass below)
   }
   // chunking: at most HP_MAX_CHUNKS chunks, each a multiple of the block size
-  int64_t chunk = (n + HP_MAX_CHUNKS - 1) / HP_MAX_CHUNKS;
+  const int64_t max_chunks = hp_max_chunks();
+  int64_t chunk = (n + max_chunks - 1) / max_chunks;
   chunk = ((chunk + HP_THREADS * 8 - 1) / (HP_THREADS * 8)) * (HP_THREADS * 8);
   const int nchunks = (int)((n + chunk - 1) / chunk);
   const size_t lds = sizeof(uint32_t) * P;
@@ -1530,6 +1555,7 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
     HIP_CHECK_LAST();
     HIP_TRY(hipMemcpyAsync(partition_offsets, starts.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream0()));
     HIP_TRY(hipStreamSynchronize(stream0()));
+    hp_note(HP_ROUTE_COLS8, fastw, murmur, nchunks, 0);
     return GDF_SUCCESS;
   }
   if (pairs) {
@@ -1551,12 +1577,14 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
     HIP_CHECK_LAST();
     HIP_TRY(hipMemcpyAsync(partition_offsets, starts.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream0()));
     HIP_TRY(hipStreamSynchronize(stream0()));
+    hp_note(HP_ROUTE_PAIRS, fastw, murmur, nchunks, 0);
     return GDF_SUCCESS;
   }
 
   // move the columns, HP_MAX_PAYLOAD_COLS per launch; a wider table records the
   // row -> destination map in the first launch and replays it for the rest
   DevBuf dst_map;
+  int map_launches = 0;
   if (num_input_cols > HP_MAX_PAYLOAD_COLS) RMM_TRY(dst_map.alloc(sizeof(uint32_t) * num_rows));
   for (int first = 0; first < num_input_cols; first += HP_MAX_PAYLOAD_COLS) {
     PayloadCols pc{};
@@ -1580,9 +1608,10 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
       }
     }
     pc.dst_map = dst_map.as<uint32_t>();
-    if (first > 0)
+    if (first > 0) {
       hipLaunchKernelGGL(part_apply_map_kernel, dim3(stream_grid(num_rows, HP_THREADS * 4)), dim3(HP_THREADS), 0, stream0(), pc, n);
-    else if (P > 16 && P <= (uint32_t)HPT_BIG_PARTS) {
+      ++map_launches;
+    } else if (P > 16 && P <= (uint32_t)HPT_BIG_PARTS) {
       // measured at 1e8 rows x 2 int64 columns: P=256 1.47 ms vs 2.83 ms direct; at P=8 the direct kernel's runs are
       // long enough already (1.10 vs 1.19 ms), so small fan-outs keep it
       // 12288-row tiles of a 1024-thread workgroup: they won over 4096-row tiles of 256 threads at EVERY fan-out the two shared
@@ -1609,6 +1638,8 @@ gdf_error gdf_hash_partition(int num_input_cols, gdf_column *input[], int column
   // partition_offsets is a HOST array (hashing.cu:499-503)
   HIP_TRY(hipMemcpyAsync(partition_offsets, starts.p, sizeof(int) * P, hipMemcpyDeviceToHost, stream0()));
   HIP_TRY(hipStreamSynchronize(stream0()));
+  hp_note(P > 16 && P <= (uint32_t)HPT_BIG_PARTS ? HP_ROUTE_TILE : fastw ? HP_ROUTE_DIRECT_FAST : HP_ROUTE_DIRECT_GENERIC, fastw, murmur, nchunks,
+          map_launches);
   return GDF_SUCCESS;
   });
 }

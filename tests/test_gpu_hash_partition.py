@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+import hash_partition_cases as hp
+from hash_partition_gpu import clear_notes, read_notes
 from oracle import oracle
 from util import ALL_DTYPES, gen_rand, random_valid
 
@@ -89,14 +91,16 @@ def test_hash_partition_pair_kernel(gdf, nparts, shape, force_path):
     """One or two 8-byte columns without masks, 16 < P <= 64, >= 2^16 rows take part_scatter_pairs_kernel (csrc/hashing.hip, round 6):
     both columns staged together, the next tile's words requested before the flush, chunks laid out XCD-major inside a partition.
     Offsets as the oracle's (hashing.cu:434-468 partition rule on the pinned Murmur3 row hash), every partition the reference's rows as a
-    multiset with rows intact -- and the same call through the generic tile kernel (GDF_HP_NO_PAIRS).  Sizes: an odd row count, and one
-    that leaves a LAST CHUNK OF ONE ROW (the kernel reads row pairs).  Reference: hashing.cu:559-654."""
+    multiset with rows intact -- and the same call with the pair kernel switched off (GDF_HP_NO_PAIRS), which the single-stage kernel
+    then takes (the hp.route note shows it; the generic tile kernel at these fan-outs is test_gpu_hash_partition_routes.py's).  Sizes: an
+    odd row count, and one that leaves a LAST CHUNK OF ONE ROW (the kernel reads row pairs).  Reference: hashing.cu:559-654."""
     n = {"last-chunk-of-one-row": 1024 * 2048 + 1}.get(shape, 1_234_567)
     k = gen_rand(np.float64 if shape == "float64-key" else np.int64, n)
     v = gen_rand(np.int64, n)
     cols, hashed = {"key-value": ([k, v], [0]), "value-key": ([v, k], [1]), "key-only": ([k], [0])}.get(shape, ([k, v], [0]))
 
     def run():
+        clear_notes(gdf)
         outs, offsets = gdf.api.hash_partition([_col(gdf, c) for c in cols], hashed, nparts)
         return [o.to_numpy() for o in outs], offsets
     perm, exp_off, pid = oracle.hash_partition(cols, hashed, nparts)
@@ -105,6 +109,9 @@ def test_hash_partition_pair_kernel(gdf, nparts, shape, force_path):
         if kernel == "generic":
             force_path("GDF_HP_NO_PAIRS")
         got, offsets = run()
+        # the route the call took (hp.route): the pair kernel, and with it switched off the single-stage kernel
+        assert read_notes(gdf)["hp.route"] == (hp.PAIRS if kernel == "pairs" else hp.COLS8)
+        assert read_notes(gdf) == hp.route_model([c.dtype for c in cols], (), (), hashed, 0, nparts, n, {} if kernel == "pairs" else {"GDF_HP_NO_PAIRS": "1"})
         assert offsets == [int(x) for x in exp_off]
         got_pid = oracle.partition_ids([got[hashed[0]]], nparts)
         for p in range(nparts):
@@ -130,6 +137,7 @@ def test_hash_partition_single_stage_kernel(gdf, nparts, shape, force_path):
                     "four-key-last": ([v[0], v[1], v[2], k], [3])}.get(shape, ([k, v[0]], [0]))
 
     def run():
+        clear_notes(gdf)
         outs, offsets = gdf.api.hash_partition([_col(gdf, c) for c in cols], hashed, nparts)
         return [o.to_numpy() for o in outs], offsets
     perm, exp_off, pid = oracle.hash_partition(cols, hashed, nparts)
@@ -138,6 +146,9 @@ def test_hash_partition_single_stage_kernel(gdf, nparts, shape, force_path):
         if kernel == "generic":
             force_path("GDF_HP_NO_COLS8")
         got, offsets = run()
+        # the route the call took (hp.route): the single-stage kernel, and with it switched off the generic tile kernel
+        assert read_notes(gdf)["hp.route"] == (hp.COLS8 if kernel == "cols8" else hp.TILE)
+        assert read_notes(gdf) == hp.route_model([c.dtype for c in cols], (), (), hashed, 0, nparts, n, {} if kernel == "cols8" else {"GDF_HP_NO_COLS8": "1"})
         assert offsets == [int(x) for x in exp_off]
         got_pid = oracle.partition_ids([got[hashed[0]]], nparts)
         for p in range(nparts):
@@ -156,6 +167,10 @@ def test_hash_partition_moves_valid_masks(gdf, nparts):
     kv, vv = random_valid(n), random_valid(n)
     outs, offsets = gdf.api.hash_partition([_col(gdf, k, kv), _col(gdf, v, vv)], [0], nparts, with_masks=True)
     gk, gv = outs[0].to_numpy(), outs[1].to_numpy()
+    # the offsets are the oracle's, and every row (a null key by its stored bytes) sits in its partition's range
+    perm, exp_off, pid = oracle.hash_partition([k, v], [0], nparts)
+    assert offsets == [int(x) for x in exp_off]
+    assert np.array_equal(oracle.partition_ids([gk], nparts), np.repeat(np.arange(nparts), np.diff(np.array(list(exp_off) + [n]))))
     gkv, gvv = outs[0].valid_bits(), outs[1].valid_bits()
     # rows (key, key_valid, value, value_valid) are preserved as a multiset
     exp = np.stack([k, kv, v, vv], axis=1).astype(np.int64)
@@ -180,7 +195,10 @@ def test_hash_partition_two_levels(gdf, nparts, keys, force_path):
     hash_cols = [0] if keys != "int32+int64" else [2, 0]
     hf = 1 if keys == "identity-int32" else 0
     cols = [k0, v, k1]
+    clear_notes(gdf)
     outs, offsets = gdf.api.hash_partition([_col(gdf, k0), _col(gdf, v, vv), _col(gdf, k1)], hash_cols, nparts, hash_func=hf, with_masks=True)
+    notes = read_notes(gdf)
+    assert notes["hp.route"] == hp.TWO_LEVEL and notes == hp.route_model([c.dtype for c in cols], {1}, {1}, hash_cols, hf, nparts, n)
     perm, exp_off, pid = oracle.hash_partition(cols, hash_cols, nparts, hf) if hf else oracle.hash_partition(cols, hash_cols, nparts)
     assert offsets == [int(x) for x in exp_off]
     got = [o.to_numpy() for o in outs]
@@ -193,8 +211,12 @@ def test_hash_partition_two_levels(gdf, nparts, keys, force_path):
     got_rows = np.stack([got_pid.astype(np.float64), got[0].astype(np.float64), np.where(gvv, got[1], -1.0), got[2].astype(np.float64)], axis=1)
     np.testing.assert_array_equal(exp_rows[np.lexsort(exp_rows.T[::-1])], got_rows[np.lexsort(got_rows.T[::-1])])
     force_path("GDF_HP_ONE_LEVEL")
+    clear_notes(gdf)
     _, offsets1 = gdf.api.hash_partition([_col(gdf, k0), _col(gdf, v, vv), _col(gdf, k1)], hash_cols, nparts, hash_func=hf, with_masks=True)
     assert offsets1 == offsets
+    notes = read_notes(gdf)                      # one level beyond 1024 partitions: a direct kernel
+    assert notes["hp.route"] == (hp.DIRECT_FAST if keys == "int64" else hp.DIRECT_GENERIC)
+    assert notes == hp.route_model([c.dtype for c in cols], {1}, {1}, hash_cols, hf, nparts, n, {"GDF_HP_ONE_LEVEL": "1"})
 
 
 @pytest.mark.parametrize("nparts", [1025, 12000, 16384])
@@ -211,7 +233,12 @@ def test_hash_partition_two_levels_pieces_and_skew(gdf, nparts, piece_rows, forc
     k0 = rs.randint(-2**40, 2**40, size=n).astype(np.int64)
     k0[rs.rand(n) < 0.33] = 123456789
     v = rs.randint(0, 2**31, size=n).astype(np.int32)
+    clear_notes(gdf)
     outs, offsets = gdf.api.hash_partition([_col(gdf, k0), _col(gdf, v)], [0], nparts)
+    notes = read_notes(gdf)
+    assert notes["hp.route"] == hp.TWO_LEVEL
+    assert notes == hp.route_model([k0.dtype, v.dtype], (), (), [0], 0, nparts, n, {} if piece_rows is None else {"GDF_HP_PIECE": str(piece_rows)})
+    assert piece_rows != 150 or notes["hp.pieces"] >= 100            # (977 level-A chunks, at most 9 of them per piece at 150 rows)
     perm, exp_off, pid = oracle.hash_partition([k0, v], [0], nparts)
     assert offsets == [int(x) for x in exp_off]
     g0, g1 = outs[0].to_numpy(), outs[1].to_numpy()
