@@ -14,7 +14,7 @@
  * The header is plain C (usable from cgo / JNI / ctypes / cffi) and is also
  * what the C++ host code in libgdf_amd/csrc compiles against.  The 182
  * element-wise operators are declared through gdf_elementwise.def.  read_csv
- * and gdf_to_csr are exported and return GDF_UNSUPPORTED_METHOD.
+ * is exported and returns GDF_UNSUPPORTED_METHOD.
  */
 #ifndef GDF_AMD_GDF_H
 #define GDF_AMD_GDF_H
@@ -148,7 +148,8 @@ typedef enum {                                                               /* 
 } window_reduction_type;
 
 /* argument PODs of the csv reader / csr converter (io_types.h:26-60,
- * convert_types.h:33-41) -- present only so the stubs have the right shape. */
+ * convert_types.h:33-41).  csv_read_arg is present only so the read_csv stub
+ * has the right shape; csr_gdf is what gdf_to_csr fills in, see below. */
 typedef struct {
   int num_cols_out; int num_rows_out; gdf_column **data;
   char *file_path; char lineterminator; char delimiter; bool delim_whitespace; bool skipinitialspace;
@@ -419,8 +420,32 @@ gdf_error   gdf_segmented_radixsort_plan_free(gdf_segmented_radixsort_plan_type 
 gdf_error   gpu_concat(gdf_column *lhs, gdf_column *rhs, gdf_column *output);
 gdf_error   gpu_hash_columns(gdf_column **columns_to_hash, int num_columns, gdf_column *output_column, void *stream);
 gdf_error   gdf_order_by(size_t nrows, gdf_column *cols, size_t ncols, void **d_cols, int *d_types, size_t *d_indx);
-/* out of scope: exported, return GDF_UNSUPPORTED_METHOD (csrc/unsupported.cpp) */
+/* out of scope: exported, returns GDF_UNSUPPORTED_METHOD (csrc/unsupported.cpp) */
 gdf_error   read_csv(csv_read_arg *args);
+
+/* --- columns to a CSR matrix (io_functions.h:22, convert_types.h:31-39; reference src/io/convert/gdf-to-csr.cu): csrc/csr.hip
+ *
+ * All num_cols columns have the same size = rows.  The result is the row-major CSR form of the rows x num_cols matrix whose
+ * entry (r, c) exists exactly when validity bit r of column c is set; a column with valid == NULL has every entry (the
+ * reference dereferences the NULL).  This converts VALIDITY, not non-zeroness: a valid 0 or NaN is an entry.  null_count is
+ * not consulted.
+ *   outputs    device memory from rmmAlloc, each released by the caller with rmmFree:
+ *              IA   gdf_size_type[rows + 1] (8-byte elements, as everywhere in this ABI); IA[0] == 0, IA[rows] == nnz;
+ *              JA   int64_t[nnz], the column indices, ascending within a row;
+ *              A    nnz elements of `dtype`.
+ *              dtype is the largest gdf_dtype enumerator among the columns (as the reference), so every conversion is a
+ *              widening static_cast in enum order: int -> wider int, int -> float32 / float64, float32 -> float64; an INT64
+ *              column next to a FLOAT32 column gives FLOAT32.  rows, cols and nnz are host fields.
+ *              nnz == 0 (rows == 0 included): GDF_SUCCESS, IA is rows + 1 zeros, A == JA == NULL (the reference answers
+ *              GDF_CUDA_ERROR and leaks its scratch).
+ *   errors     on any error nothing stays allocated and *csrReturn is untouched.  Host checks before any device work:
+ *              csrReturn == NULL: GDF_INVALID_API_CALL.  gdfData == NULL, num_cols <= 0, a NULL element, or rows > 0 with a
+ *              NULL data pointer: GDF_DATASET_EMPTY.  Sizes differ: GDF_COLUMN_SIZE_MISMATCH (the reference never looks).  A
+ *              column dtype outside INT8 .. FLOAT64: GDF_UNSUPPORTED_DTYPE.  After the count pass: nnz > INT32_MAX (the tile
+ *              offsets are 32-bit): GDF_COLUMN_SIZE_TOO_BIG.
+ *   masks      bits of the last mask byte beyond `rows` are ignored; a mask pointer needs no alignment.
+ *   determinism  no atomics touch the outputs: a second call on the same input gives bit-identical A, IA and JA.
+ *   stream     the legacy default stream; the call returns after the outputs are written.                                     */
 gdf_error   gdf_to_csr(gdf_column **gdfData, int num_cols, csr_gdf *csrReturn);
 
 #if defined(__GNUC__)

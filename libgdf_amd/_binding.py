@@ -53,6 +53,20 @@ class gdf_context(C.Structure):
     ]
 
 
+class csr_gdf(C.Structure):
+    """56-byte POD filled in by gdf_to_csr, reference include/gdf/cffi/convert_types.h:31-39.  A, IA (size_t elements) and JA
+    (int64 elements) are device pointers owned by the caller (rmmFree); dtype, nnz, rows and cols are host values."""
+    _fields_ = [
+        ("A", C.c_void_p),
+        ("IA", C.c_void_p),
+        ("JA", C.c_void_p),
+        ("dtype", C.c_int),
+        ("nnz", C.c_int64),
+        ("rows", C.c_size_t),
+        ("cols", C.c_size_t),
+    ]
+
+
 class rmmOptions_t(C.Structure):
     _fields_ = [("allocation_mode", C.c_int), ("initial_pool_size", C.c_size_t), ("enable_logging", C.c_bool)]
 
@@ -151,6 +165,8 @@ _PROTOTYPES = {
     # HOST pointer (a double for exact, a T for approx)
     "gdf_quantile_exact": (None, [_COLP, C.c_int, C.c_double, C.c_void_p, _CTXP]),
     "gdf_quantile_aprrox": (None, [_COLP, C.c_double, C.c_void_p, _CTXP]),
+    # columns -> CSR (csrc/csr.hip)
+    "gdf_to_csr": (None, [_COLPP, C.c_int, C.POINTER(csr_gdf)]),
 }
 for _op in ("sum", "product", "min", "max", "sum_squared"):
     for _sfx in (("generic", "f64", "f32") if _op == "sum_squared" else ("generic", "f64", "f32", "i64", "i32", "i8")):

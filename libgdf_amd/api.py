@@ -11,8 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._binding import (BINARY_OPS, CAST_TARGETS, DATETIME_FIELDS, GDF_UNSUPPORTED_METHOD, MATH_OPS, GDFError, gdf_column,
-                       libgdf)
+from ._binding import (BINARY_OPS, CAST_TARGETS, DATETIME_FIELDS, GDF_UNSUPPORTED_METHOD, MATH_OPS, GDFError, csr_gdf,
+                       gdf_column, libgdf, librmm)
 from .columns import (GDF_DTYPES, GDF_HASH, GDF_HASH_MURMUR3, GDF_SORT, GDF_TO_NP, TIME_UNITS, Column, column_array,
                       new_context)
 
@@ -371,6 +371,31 @@ def quantile(col: Column, q: float, method=None, sorted=False, sort_inplace=Fals
     res = C.c_double(0.0)
     libgdf.gdf_quantile_exact(col.ptr, prec, float(q), C.addressof(res), C.byref(ctx))
     return res.value
+
+
+def to_csr(cols):
+    """gdf_to_csr: the CSR form (A, IA, JA) of the rows x len(cols) matrix whose entry (r, c) exists where column c is valid at
+    row r (a column without a mask has every entry).  A has the widest dtype among the columns, JA is int64.  The library's IA
+    holds 8-byte gdf_size_type elements; nnz <= INT32_MAX is part of the contract, so IA is returned as int32.  The three
+    buffers are copied device-to-device into torch tensors and the library's are released with rmmFree."""
+    import torch
+    csr = csr_gdf()
+    arr = column_array(cols)
+    libgdf.gdf_to_csr(arr, len(cols), C.byref(csr))
+    try:
+        nnz, rows = int(csr.nnz), int(csr.rows)
+        A = torch.empty(nnz, dtype=getattr(torch, np.dtype(GDF_TO_NP[int(csr.dtype)]).name), device="cuda")
+        IA = torch.empty(rows + 1, dtype=torch.int64, device="cuda")
+        JA = torch.empty(nnz, dtype=torch.int64, device="cuda")
+        _hipMemcpyDtoD(IA.data_ptr(), csr.IA, IA.numel() * 8)
+        if nnz:
+            _hipMemcpyDtoD(A.data_ptr(), csr.A, nnz * A.element_size())
+            _hipMemcpyDtoD(JA.data_ptr(), csr.JA, nnz * 8)
+    finally:
+        for p in (csr.A, csr.IA, csr.JA):
+            if p:
+                librmm.rmmFree(p, None)
+    return A, IA.to(torch.int32), JA
 
 
 # ---- element-wise operators (csrc/elementwise.hip) ---------------------------------------------------------------------------
