@@ -13,8 +13,9 @@
  *
  * The header is plain C (usable from cgo / JNI / ctypes / cffi) and is also
  * what the C++ host code in libgdf_amd/csrc compiles against.  The 182
- * element-wise operators are declared through gdf_elementwise.def.  read_csv
- * is exported and returns GDF_UNSUPPORTED_METHOD.
+ * element-wise operators are declared through gdf_elementwise.def.  Every
+ * entry point does real work; none answers GDF_UNSUPPORTED_METHOD for
+ * being out of scope.
  */
 #ifndef GDF_AMD_GDF_H
 #define GDF_AMD_GDF_H
@@ -148,8 +149,8 @@ typedef enum {                                                               /* 
 } window_reduction_type;
 
 /* argument PODs of the csv reader / csr converter (io_types.h:26-60,
- * convert_types.h:33-41).  csv_read_arg is present only so the read_csv stub
- * has the right shape; csr_gdf is what gdf_to_csr fills in, see below. */
+ * convert_types.h:33-41).  csv_read_arg carries the arguments and the three
+ * output fields of read_csv; csr_gdf is what gdf_to_csr fills in, see below. */
 typedef struct {
   int num_cols_out; int num_rows_out; gdf_column **data;
   char *file_path; char lineterminator; char delimiter; bool delim_whitespace; bool skipinitialspace;
@@ -420,7 +421,78 @@ gdf_error   gdf_segmented_radixsort_plan_free(gdf_segmented_radixsort_plan_type 
 gdf_error   gpu_concat(gdf_column *lhs, gdf_column *rhs, gdf_column *output);
 gdf_error   gpu_hash_columns(gdf_column **columns_to_hash, int num_columns, gdf_column *output_column, void *stream);
 gdf_error   gdf_order_by(size_t nrows, gdf_column *cols, size_t ncols, void **d_cols, int *d_types, size_t *d_indx);
-/* out of scope: exported, returns GDF_UNSUPPORTED_METHOD (csrc/unsupported.cpp) */
+
+/* --- delimited text to columns (io_functions.h:18, io_types.h:26-60; reference src/io/csv/csv-reader.cu, type_conversion.cuh,
+ *     date-time-parser.cuh): csrc/csv.hip
+ *
+ * The reference is the model for what the arguments mean, not for its arithmetic; every DEVIATION is marked with the reference
+ * line it departs from.  The file is bytes; no quoting (a quote character is an ordinary byte, as in the reference), no header row.
+ *   arguments  names, dtype and num_cols are required.  dtype strings (csv-reader.cu:393-413): str, category -> GDF_CATEGORY; date,
+ *              date64 -> GDF_DATE64; date32 -> GDF_DATE32; timestamp -> GDF_TIMESTAMP; float, float32 -> GDF_FLOAT32; float64,
+ *              double -> GDF_FLOAT64; short -> GDF_INT16; int, int32 -> GDF_INT32; int64, long -> GDF_INT64.
+ *              delimiter separates fields; delim_whitespace makes it one space (two spaces enclose an empty field), as the
+ *              reference.  lineterminator ends a record; when it is '\n', one '\r' directly in front of it is not part of the
+ *              record.  skiprows / skipfooter drop records from the front / the back (dropping all of them: zero rows, success).
+ *              skipinitialspace drops the leading spaces of CATEGORY fields; fields of every other dtype are always trimmed of
+ *              spaces (0x20) on both sides.  dayfirst: see dates.
+ *   records    every terminator ends a record; a non-empty tail behind the last terminator is a record too (DEVIATION:
+ *              csv-reader.cu:505-535 counts terminators only and drops it; :528, :595 and :686 look at the byte behind the last
+ *              one, this library reads nothing outside the file's bytes).  An empty record is a row of nulls.  Row r, column c is
+ *              the c-th delimiter-separated field of record skiprows + r; a record with fewer than num_cols fields has nulls in
+ *              the missing ones, fields beyond num_cols are ignored.
+ *   nulls      an empty field (after the trimming above) is null, and so is a field that is not a literal of its column's dtype
+ *              as defined below.  A null element has validity bit 0 and data element 0 (DEVIATION: csv-reader.cu:460 leaves the
+ *              data uninitialised), so whole arrays compare equal.
+ *   integers   INT16, INT32, INT64 and TIMESTAMP (int64, time_unit TIME_UNIT_NONE): [+-]? digit (digit | ',')* where every ','
+ *              stands between two digits and is skipped -- the reference's thousands separator, type_conversion.cuh:70; it can
+ *              only occur when the delimiter is another byte.  DEVIATION: a sign is understood (type_conversion.cuh:47-79 turns
+ *              '-' into a digit of value -3), and a value outside the dtype's range is null, not wrapped.
+ *   floats     [+-]? (digits [. digits*] | . digits) ([eE] [+-]? digits)?, commas in the integer part as above; inf, nan and
+ *              hexadecimal forms are no literals (null).  The first 19 significant digits (leading zeros are not significant)
+ *              are kept in a 64-bit integer m, every further digit is dropped, and the decimal exponent e absorbs the dropped
+ *              integer digits, the kept fraction digits and the written exponent: the field stands for m * 10^e, truncated after
+ *              19 digits.  m == 0 gives a zero; e > 308 gives an infinity; e < -400 a zero.  Otherwise x = (double)m, then
+ *                e >= 0:  x * P[e / 22] * 10^(e % 22)           e < 0:  [x / 1e308 first when e < -308, e += 308]
+ *                                                                        x / 10^(|e| % 22) / P[|e| / 22]
+ *              with P[q] the double nearest to 10^(22 q) and 10^0 .. 10^22 exact doubles.  FAST DOMAIN m < 2^53 and |e| <= 22:
+ *              (double)m is exact, P[0] = 1 and P[1] = 1e22 are exact, one of the two factors is 1: ONE rounding, the correctly
+ *              rounded value (Clinger's fast path) -- bit-equal to strtod / Python's float().  OUTSIDE it the roundings are:
+ *              (double)m; 1e308 and its division; P[q] and its operation; the operation with 10^r -- at most six, each a relative
+ *              error of at most 2^-53, which is half an ulp at the top of a binade and one ulp at its bottom.  Their sum puts the
+ *              result within 6 ulp of m * 10^e; dropping digits beyond the 19th moves m * 10^e by less than 10^-18 of itself
+ *              (under 0.01 ulp); the correctly rounded value is half an ulp from the exact one: the result is within 7 ulp (of
+ *              the correctly rounded value) of it.  An intermediate never exceeds the final magnitude for e >= 0 (no early
+ *              overflow); for e < 0 an intermediate that is already subnormal is divided further, which shrinks its absolute
+ *              error below the final half ulp.  Overflow gives +-inf -- and so may a literal within those 7 ulp of the largest
+ *              finite double -- and a written "-0" gives -0.0.  A written exponent saturates at 4 * 10^18 in magnitude, beyond
+ *              the digit count of any field (a buffer has at most 2^62 bytes), before it is added to the digits' exponent and
+ *              the sum is compared with 308 and -400.  FLOAT32 is (float) of that double.  (DEVIATION:
+ *              type_conversion.cuh:82-152 sums digit * pow(10, k) in the column type, knows no sign and no exponent.)
+ *   dates      DATE32: days since 1970-01-01 in the proleptic Gregorian calendar, correct on both sides of the epoch (DEVIATION:
+ *              date-time-parser.cuh:324-351 is a day ahead -- it adds the day of the month to days that already count from day
+ *              1 -- and knows leap years by year % 4 only); DATE64 the same in milliseconds.  Date forms, the separator being
+ *              '/' or '-' (the same one twice), Y four digits, M and D one or two:  Y-M-D, Y-M (a four-digit first part is the
+ *              year);  M-D-Y, or D-M-Y with dayfirst;  M-Y.  A missing day is 1.  DATE64 only: a time may follow after 'T' or
+ *              one space, as H:M or H:M:S (one or two digits each), optionally followed by AM or PM (either case, optionally
+ *              after one space); with AM / PM the hour is 1 .. 12, 12 AM is hour 0 and 12 PM hour 12 (DEVIATION:
+ *              date-time-parser.cuh:274-291 adds 12 to every PM hour: 12 PM becomes 24).  Checked: year 1 .. 9999, month
+ *              1 .. 12, day within the month (leap years by the Gregorian rule), hour 0 .. 23, minute and second 0 .. 59; a
+ *              failure, or anything else behind the date or time, is null.
+ *   category   MurmurHash3 x86_32 with seed 33 of exactly the field's bytes, as int32 (DEVIATION: csv-reader.cu:763 hashes
+ *              through the delimiter or terminator behind the field).
+ *   outputs    args->data, num_cols_out (= num_cols) and num_rows_out are set.  data is a malloc'ed array of num_cols malloc'ed
+ *              gdf_columns, each with a malloc'ed copy of its name in col_name; data and valid inside each column come from
+ *              rmmAlloc and are released by gdf_column_free (the reference's split of ownership; gdf_amd_read_csv_release in
+ *              gdf_amd_ext.h releases all of it).  Per column: size = rows, dtype, null_count exact, every other field zero.
+ *              valid is never NULL when rows > 0, has ceil(rows / 64) * 8 >= ceil(rows / 8) bytes, LSB first, and the bits
+ *              beyond `rows` are 0.  Zero rows: size 0 and data == valid == NULL.  CATEGORY data is int32.
+ *   errors     all argument errors are reported before any device work and before the file is opened; on any error the three
+ *              output fields are untouched and nothing stays allocated.  GDF_INVALID_API_CALL: args NULL, num_cols <= 0, names
+ *              or dtype NULL or with a NULL element, a negative skip count.  Then GDF_UNSUPPORTED_DTYPE: an unknown dtype string.
+ *              Then GDF_FILE_ERROR: file_path NULL, the file cannot be opened or mapped, or is not a regular file.  After the
+ *              count pass GDF_COLUMN_SIZE_TOO_BIG: more than INT32_MAX records.  An empty file is zero rows, no error.
+ *   determinism  a second call on the same bytes gives bit-identical columns and masks (the only atomics add up null counts).
+ *   stream     the legacy default stream; the call returns after the outputs are written.                                     */
 gdf_error   read_csv(csv_read_arg *args);
 
 /* --- columns to a CSR matrix (io_functions.h:22, convert_types.h:31-39; reference src/io/convert/gdf-to-csr.cu): csrc/csr.hip

@@ -263,6 +263,20 @@ gdf_error gdf_amd_rccl_transport_ranks(gdf_amd_transport *transport, int *nranks
    1: host -> device, 2: device -> device */
 gdf_error gdf_amd_copy(void *dst, const void *src, size_t bytes, int direction);
 
+/*
+ * read_csv (include/gdf/gdf.h has the contract) over bytes that already sit in DEVICE memory: the same reader, fields and errors,
+ * with args->file_path ignored.  d_bytes needs no alignment and nothing outside [d_bytes, d_bytes + num_bytes) is read; the bytes
+ * are not modified and may be released as soon as the call returns.  num_bytes == 0 (d_bytes may then be NULL) is the empty file;
+ * d_bytes == NULL with num_bytes > 0 is GDF_INVALID_API_CALL.  read_csv itself is open + fstat + mmap + one upload + this call.
+ */
+gdf_error gdf_amd_read_csv_device(const char *d_bytes, size_t num_bytes, csv_read_arg *args);
+/*
+ * Releases everything a successful read_csv / gdf_amd_read_csv_device returned in args: the columns' device memory
+ * (gdf_column_free), their names, the column structs and the array; then zeroes args->data, num_cols_out and num_rows_out.
+ * Calling it again on the zeroed fields does nothing.  args == NULL: GDF_INVALID_API_CALL.
+ */
+gdf_error gdf_amd_read_csv_release(csv_read_arg *args);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

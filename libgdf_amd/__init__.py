@@ -19,6 +19,7 @@ from ._binding import (  # noqa: F401
     GDFError,
     RMMError,
     csr_gdf,
+    csv_read_arg,
     gdf_column,
     gdf_context,
     libgdf,
@@ -37,10 +38,10 @@ from .columns import (  # noqa: F401
     new_context,
 )
 from . import api  # noqa: F401
-from .api import to_csr  # noqa: F401
+from .api import read_csv, to_csr  # noqa: F401
 
 __all__ = [
-    "GDFError", "RMMError", "csr_gdf", "gdf_column", "gdf_context", "libgdf", "librmm", "LIB_DIR",
+    "GDFError", "RMMError", "csr_gdf", "csv_read_arg", "gdf_column", "gdf_context", "libgdf", "librmm", "LIB_DIR",
     "GDF_DTYPES", "NP_TO_GDF", "Column", "buffer_as_bits", "column_from_tensor", "get_dtype",
-    "mask_from_bools", "new_column", "new_context", "api", "to_csr",
+    "mask_from_bools", "new_column", "new_context", "api", "read_csv", "to_csr",
 ]

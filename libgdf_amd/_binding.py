@@ -67,6 +67,27 @@ class csr_gdf(C.Structure):
     ]
 
 
+class csv_read_arg(C.Structure):
+    """Arguments and the three output fields of read_csv, reference include/gdf/cffi/io_types.h:26-60.  data is a malloc'ed
+    array of malloc'ed gdf_columns (gdf_amd_read_csv_release frees all of it); names and dtype are arrays of C strings."""
+    _fields_ = [
+        ("num_cols_out", C.c_int),
+        ("num_rows_out", C.c_int),
+        ("data", C.POINTER(C.POINTER(gdf_column))),
+        ("file_path", C.c_char_p),
+        ("lineterminator", C.c_char),
+        ("delimiter", C.c_char),
+        ("delim_whitespace", C.c_bool),
+        ("skipinitialspace", C.c_bool),
+        ("num_cols", C.c_int),
+        ("names", C.POINTER(C.c_char_p)),
+        ("dtype", C.POINTER(C.c_char_p)),
+        ("skiprows", C.c_int),
+        ("skipfooter", C.c_int),
+        ("dayfirst", C.c_bool),
+    ]
+
+
 class rmmOptions_t(C.Structure):
     _fields_ = [("allocation_mode", C.c_int), ("initial_pool_size", C.c_size_t), ("enable_logging", C.c_bool)]
 
@@ -167,6 +188,10 @@ _PROTOTYPES = {
     "gdf_quantile_aprrox": (None, [_COLP, C.c_double, C.c_void_p, _CTXP]),
     # columns -> CSR (csrc/csr.hip)
     "gdf_to_csr": (None, [_COLPP, C.c_int, C.POINTER(csr_gdf)]),
+    # delimited text -> columns (csrc/csv.hip); the device-buffer form takes a DEVICE address as an integer
+    "read_csv": (None, [C.POINTER(csv_read_arg)]),
+    "gdf_amd_read_csv_device": (None, [C.c_void_p, C.c_size_t, C.POINTER(csv_read_arg)]),
+    "gdf_amd_read_csv_release": (None, [C.POINTER(csv_read_arg)]),
 }
 for _op in ("sum", "product", "min", "max", "sum_squared"):
     for _sfx in (("generic", "f64", "f32") if _op == "sum_squared" else ("generic", "f64", "f32", "i64", "i32", "i8")):

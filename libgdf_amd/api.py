@@ -8,11 +8,12 @@ torch tensors with a device-to-device hipMemcpy and released with ``gdf_column_f
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
 from ._binding import (BINARY_OPS, CAST_TARGETS, DATETIME_FIELDS, GDF_UNSUPPORTED_METHOD, MATH_OPS, GDFError, csr_gdf,
-                       gdf_column, libgdf, librmm)
+                       csv_read_arg, gdf_column, libgdf, librmm)
 from .columns import (GDF_DTYPES, GDF_HASH, GDF_HASH_MURMUR3, GDF_SORT, GDF_TO_NP, TIME_UNITS, Column, column_array,
                       new_context)
 
@@ -396,6 +397,53 @@ def to_csr(cols):
             if p:
                 librmm.rmmFree(p, None)
     return A, IA.to(torch.int32), JA
+
+
+def csv_args(names, dtypes, path=None, delimiter=",", lineterminator="\n", delim_whitespace=False, skipinitialspace=False,
+             skiprows=0, skipfooter=0, dayfirst=False):
+    """A filled-in csv_read_arg; the ctypes string arrays it points to are kept alive on the object."""
+    if len(names) != len(dtypes):
+        raise ValueError("names and dtypes differ in length")
+    a = csv_read_arg()
+    a._keep = ((C.c_char_p * len(names))(*[n.encode() for n in names]), (C.c_char_p * len(dtypes))(*[d.encode() for d in dtypes]))
+    a.names, a.dtype, a.num_cols = a._keep[0], a._keep[1], len(names)
+    a.file_path = None if path is None else os.fsencode(path)
+    a.delimiter, a.lineterminator = delimiter.encode(), lineterminator.encode()
+    a.delim_whitespace, a.skipinitialspace, a.dayfirst = bool(delim_whitespace), bool(skipinitialspace), bool(dayfirst)
+    a.skiprows, a.skipfooter = int(skiprows), int(skipfooter)
+    return a
+
+
+def take_csv_result(a: csv_read_arg):
+    """{name: (data tensor, mask tensor, null_count)} of a successful read_csv / gdf_amd_read_csv_device call, copied device to
+    device into torch tensors; the C result is released with gdf_amd_read_csv_release whatever happens.  The mask tensor holds
+    ceil(rows / 8) bytes, LSB first."""
+    import torch
+    try:
+        out = {}
+        rows = int(a.num_rows_out)
+        for c in range(int(a.num_cols_out)):
+            col = a.data[c].contents
+            dtype = int(col.dtype)
+            npt = np.dtype(np.int32) if dtype == GDF_DTYPES["GDF_CATEGORY"] else np.dtype(GDF_TO_NP[dtype])
+            data = torch.empty(rows, dtype=getattr(torch, npt.name), device="cuda")
+            mask = torch.empty((rows + 7) // 8, dtype=torch.uint8, device="cuda")
+            if rows:
+                _hipMemcpyDtoD(data.data_ptr(), col.data, rows * data.element_size())
+                _hipMemcpyDtoD(mask.data_ptr(), col.valid, mask.numel())
+            out[col.col_name.decode()] = (data, mask, int(col.null_count))
+        return out
+    finally:
+        libgdf.gdf_amd_read_csv_release(C.byref(a))
+
+
+def read_csv(path, names, dtypes, delimiter=",", lineterminator="\n", delim_whitespace=False, skipinitialspace=False, skiprows=0,
+             skipfooter=0, dayfirst=False):
+    """read_csv: the file at `path` as columns `names` of the dtype strings `dtypes` (include/gdf/gdf.h has the contract and the
+    strings).  Returns {name: (data tensor, mask tensor, null_count)}; CATEGORY columns come as the int32 hashes of their fields."""
+    a = csv_args(names, dtypes, path, delimiter, lineterminator, delim_whitespace, skipinitialspace, skiprows, skipfooter, dayfirst)
+    libgdf.read_csv(C.byref(a))
+    return take_csv_result(a)
 
 
 # ---- element-wise operators (csrc/elementwise.hip) ---------------------------------------------------------------------------
