@@ -587,6 +587,16 @@ __global__ __launch_bounds__(LB_THREADS) void scan_lookback(const ELEM *in, ELEM
   }
 }
 
+// The family whose kernels produced the output, noted for the tests (lab::note): "scan.route" 0 element-wise,
+// 1 coalesced, 2 look-back, 3 spine, 4 rounds; "scan.chunks" / "scan.chunk_elems" the geometry of the three-launch families (0 for a
+// single pass).  Next to them "scan.grid", the workgroups of the last single-pass launch (0: none), and "scan.bailed", 1 when a rounds
+// launch bailed out and the three launches started over.  One null-pointer test each without the hook library.
+static void note_scan_route(int route, long long chunks, long long chunk_elems) {
+  lab::note("scan.route", route);
+  lab::note("scan.chunks", chunks);
+  lab::note("scan.chunk_elems", chunk_elems);
+}
+
 template <class ACC, class ELEM, bool ROUNDS>
 static gdf_error device_scan_lookback_impl(const ELEM *in, ELEM *out, size_t n, bool inclusive, long long mode) {
   constexpr int NW = sizeof(ACC) / 4;
@@ -617,13 +627,16 @@ static gdf_error device_scan_lookback_impl(const ELEM *in, ELEM *out, size_t n, 
   GDF_LAUNCH(ROUNDS ? "scan_rounds" : "scan_lookback", (scan_lookback<ACC, ELEM, ROUNDS>), dim3((unsigned)grid), dim3(LB_THREADS), 0, stream0(), in, out, n,
              inclusive ? 1 : 0, st.as<unsigned long long>(), ticket, (uint32_t)ntiles, mode_bits);
   HIP_CHECK_LAST();
+  lab::note("scan.grid", (long long)grid);
   if (ROUNDS) {                               // a grid that was not resident bailed out -- the caller takes the three launches
     uint32_t bailed = 0;
     HIP_TRY(read_back(&bailed, ticket + 1, sizeof(bailed)));
     if (bailed) return GDF_UNSUPPORTED_METHOD;
-    return GDF_SUCCESS;
+  } else {
+    HIP_TRY(hipStreamSynchronize(stream0()));   // scratch is released on return
   }
-  HIP_TRY(hipStreamSynchronize(stream0()));   // scratch is released on return
+  note_scan_route(ROUNDS ? 4 : (mode == 2 ? 3 : 2), 0, 0);
+  lab::note("scan.bailed", 0);
   return GDF_SUCCESS;
 }
 template <class ACC, class ELEM>
@@ -773,7 +786,7 @@ __global__ __launch_bounds__(LB_THREADS) void scan_apply_v(const ELEM *in, ELEM 
 }
 
 template <class ACC, class ELEM>
-static gdf_error device_scan_coalesced(const ELEM *in, ELEM *out, size_t n, bool inclusive, DevBuf *keep = nullptr) {
+static gdf_error device_scan_coalesced(const ELEM *in, ELEM *out, size_t n, bool inclusive, DevBuf *keep = nullptr, bool after_bail = false) {
   DevBuf local;
   DevBuf &sums = keep ? *keep : local;         // keep: the caller holds the scratch, nothing waits here
   RMM_TRY(sums.alloc(sizeof(ACC) * SCAN_MAX_CHUNKS));
@@ -787,6 +800,9 @@ static gdf_error device_scan_coalesced(const ELEM *in, ELEM *out, size_t n, bool
              inclusive ? 1 : 0);
   HIP_CHECK_LAST();
   if (!keep) HIP_TRY(hipStreamSynchronize(stream0()));   // scratch is released on return
+  note_scan_route(1, nchunks, (long long)chunk);
+  lab::note("scan.bailed", after_bail ? 1 : 0);
+  if (!after_bail) lab::note("scan.grid", 0);              // (after a bail-out: the rounds' grid stays noted)
   return GDF_SUCCESS;
 }
 
@@ -810,11 +826,13 @@ gdf_error device_scan(const ELEM *in, ELEM *out, size_t n, bool inclusive) {
   if (mode < 0) mode = (n >= SCAN_ROUNDS_MIN && sizeof(ELEM) >= 4) ? 3 : 0;
   if (mode == 3 && (const void *)in == (const void *)out) mode = 0;
   if (!blocked && ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0)) {
+    bool bailed = false;
     if (mode > 0 && n / LB_TILE < 0x7fffffffULL) {
       const gdf_error e = device_scan_lookback<ACC, ELEM>(in, out, n, inclusive, mode);
       if (e != GDF_UNSUPPORTED_METHOD) return e;
+      bailed = true;
     }
-    return device_scan_coalesced<ACC, ELEM>(in, out, n, inclusive);
+    return device_scan_coalesced<ACC, ELEM>(in, out, n, inclusive, nullptr, bailed);
   }
   constexpr int ITEMS = 16 / sizeof(ELEM) >= 4 ? 8 : 4;
   constexpr size_t TILE = (size_t)SCAN_THREADS * ITEMS;
@@ -833,6 +851,9 @@ gdf_error device_scan(const ELEM *in, ELEM *out, size_t n, bool inclusive) {
              inclusive ? 1 : 0);
   HIP_CHECK_LAST();
   HIP_TRY(hipStreamSynchronize(stream0()));   // scratch is released on return
+  note_scan_route(0, nchunks, (long long)chunk);
+  lab::note("scan.bailed", 0);
+  lab::note("scan.grid", 0);
   return GDF_SUCCESS;
 }
 

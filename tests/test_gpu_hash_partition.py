@@ -270,9 +270,11 @@ def test_prefixsum(gdf, dtype, n, inclusive):
 
 @pytest.mark.parametrize("dtype", [np.int8, np.int32, np.int64])
 def test_prefixsum_many_tiles_unaligned_and_in_place(gdf, dtype):
-    """The single-pass (decoupled look-back) scan over thousands of tiles -- every tile waits for its predecessors, in
-    whatever order the hardware runs them -- repeated, so that a lost or torn publication would show; a column that starts
-    1 element into a buffer (no 16-byte alignment: the three-pass kernels); and in == out."""
+    """The single-pass scan in lockstep rounds (scan_lookback<.., ROUNDS>, the default at this size for int32 / int64; int8 takes the
+    three coalesced launches) over thousands of tiles -- every workgroup waits for the others' aggregates of its round, in whatever
+    order the hardware runs them -- repeated, so that a lost or torn publication would show; a column that starts 1 element into a
+    buffer (no 16-byte alignment: the element-wise kernels); and in == out (never the rounds: the coalesced kernels).
+    test_gpu_prefixsum.py asserts these routes from the library's notes."""
     import torch
     from libgdf_amd import Column, libgdf
     n = 30_000_001
