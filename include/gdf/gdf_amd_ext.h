@@ -1,7 +1,8 @@
 /*
  * gdf_amd_ext.h -- exports of libgdf.so that the reference does NOT have.  Nothing here is needed by a
- * caller of the reference API; they exist for measurement (bench.py, tools/), for tests, and for the multi-GPU
- * layer (libgdf_amd/multigpu.py), which sits above the unchanged gdf_* ABI.
+ * caller of the reference API; they exist for measurement (bench.py, tools/), for tests, for the multi-GPU
+ * layer (libgdf_amd/multigpu.py), which sits above the unchanged gdf_* ABI, and for what the reference ABI cannot
+ * express: a CSV reader over device bytes, ORDER BY over masked columns with a direction per column, a row gather.
  */
 #ifndef GDF_AMD_EXT_H
 #define GDF_AMD_EXT_H
@@ -276,6 +277,54 @@ gdf_error gdf_amd_read_csv_device(const char *d_bytes, size_t num_bytes, csv_rea
  * Calling it again on the zeroed fields does nothing.  args == NULL: GDF_INVALID_API_CALL.
  */
 gdf_error gdf_amd_read_csv_release(csv_read_arg *args);
+
+/*
+ * gdf_amd_order_by_ex -- ORDER BY that honours validity masks, with a direction and a null placement per column (csrc/order.hip).
+ * gdf_order_by itself stays as the reference has it: ascending only, a mask is GDF_VALIDITY_UNSUPPORTED -- so a table that read_csv
+ * returned (every column masked) is sorted through this entry.  out_indices receives the STABLE lexicographic row permutation.
+ *
+ *   cols         1 ... 16 key columns of equal size; the dtypes gdf_order_by takes (INT8 ... FLOAT64, DATE32, DATE64, TIMESTAMP)
+ *   flags        HOST array of ncols bytes, GDF_AMD_ORDER_DESC | GDF_AMD_ORDER_NULLS_FIRST per column; NULL: all zero
+ *   out_indices  caller-preallocated GDF_INT32 column without a mask, size == rows
+ *
+ * Value order  as gdf_order_by: integers signed, -0.0 == +0.0, every NaN equal to every other NaN and greater than +inf.  DESC is
+ *              the exact reverse of that order, so NaN comes first among the values of a descending column.
+ * Nulls        a row is null in column c when c has a mask and its bit is 0 (LSB first).  All nulls of a column compare equal and
+ *              stand AFTER all its values, or before them with NULLS_FIRST -- whatever DESC says (SQL's absolute placement).  The
+ *              data under a null bit is never compared and does not widen the integer range the images are built from.  valid ==
+ *              NULL means no nulls; null_count is not consulted; mask bits beyond size are ignored; the mask needs no alignment.
+ * Stability    rows that compare equal on all columns keep their input order, also under DESC (a reversed ascending sort is not
+ *              this).  With no masks and all flags zero the permutation is gdf_order_by's, element for element.
+ * Errors       all checked on the host before any device work, out_indices untouched: cols NULL, ncols <= 0 or a NULL element ->
+ *              GDF_DATASET_EMPTY; ncols > 16 -> GDF_JOIN_TOO_MANY_COLUMNS; sizes differ -> GDF_COLUMN_SIZE_MISMATCH; a key dtype
+ *              outside the list -> GDF_UNSUPPORTED_DTYPE; a flag byte with other bits -> GDF_INVALID_API_CALL; out_indices NULL, not
+ *              GDF_INT32, of another size, or data == NULL with rows > 0 -> GDF_INVALID_API_CALL; out_indices with a mask ->
+ *              GDF_VALIDITY_UNSUPPORTED; rows >= 2^31 - 1 -> GDF_COLUMN_SIZE_TOO_BIG.  rows == 0: success, nothing written.
+ * Determinism  a second call on the same input gives a bit-identical result.  Runs on the legacy default stream and returns after
+ *              the output is written.
+ */
+#define GDF_AMD_ORDER_DESC        1u   /* this column descending                          */
+#define GDF_AMD_ORDER_NULLS_FIRST 2u   /* its nulls before every value (default: after)   */
+gdf_error gdf_amd_order_by_ex(gdf_column **cols, int ncols, const uint8_t *flags, gdf_column *out_indices);
+
+/*
+ * gdf_amd_gather -- outs[c][i] = cols[c][indices[i]]: turns a row permutation (gdf_amd_order_by_ex) or the index columns of
+ * gdf_inner_join / gdf_left_join / gdf_full_join, where -1 marks the missing side, into columns (csrc/order.hip).
+ *
+ *   indices   GDF_INT32 or GDF_INT64 without a mask, m rows; every value in [0, rows) or -1
+ *   cols      ncols >= 1 source columns of equal size `rows`, any dtype get_column_byte_width knows; masks honoured
+ *   outs      ncols column structs the call fills in: data and valid from rmmAlloc (release with gdf_column_free), size m, dtype
+ *             and dtype_info of cols[c].  ALWAYS with a mask of ceil(m / 64) * 8 bytes whose bits beyond m are zero, and an exact
+ *             null_count.  Row i is null -- with data element 0, so whole arrays compare equal -- where indices[i] is -1 or the
+ *             source row is null.  m == 0: size 0, data == valid == NULL.
+ *
+ * Errors      nothing stays allocated, outs untouched: NULL arguments (also an element of cols / outs, or data of a column with rows)
+ *             or ncols <= 0 -> GDF_DATASET_EMPTY; source sizes differ -> GDF_COLUMN_SIZE_MISMATCH; another index dtype or a source
+ *             dtype without a byte width -> GDF_UNSUPPORTED_DTYPE; indices with a mask -> GDF_VALIDITY_UNSUPPORTED; an index < -1 or
+ *             >= rows -> GDF_INVALID_API_CALL (found on the device; no address outside a source column is ever formed from it).
+ * Determinism and stream as gdf_amd_order_by_ex.
+ */
+gdf_error gdf_amd_gather(gdf_column *indices, int ncols, gdf_column **cols, gdf_column **outs);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -192,6 +192,9 @@ _PROTOTYPES = {
     "read_csv": (None, [C.POINTER(csv_read_arg)]),
     "gdf_amd_read_csv_device": (None, [C.c_void_p, C.c_size_t, C.POINTER(csv_read_arg)]),
     "gdf_amd_read_csv_release": (None, [C.POINTER(csv_read_arg)]),
+    # null-aware ORDER BY and the row gather (csrc/order.hip); flags is a HOST array of bytes
+    "gdf_amd_order_by_ex": (None, [_COLPP, C.c_int, C.POINTER(C.c_uint8), _COLP]),
+    "gdf_amd_gather": (None, [_COLP, C.c_int, _COLPP, _COLPP]),
 }
 for _op in ("sum", "product", "min", "max", "sum_squared"):
     for _sfx in (("generic", "f64", "f32") if _op == "sum_squared" else ("generic", "f64", "f32", "i64", "i32", "i8")):

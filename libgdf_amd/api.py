@@ -141,6 +141,57 @@ def order_by(cols):
     return d_indx[:n]
 
 
+ORDER_DESC, ORDER_NULLS_FIRST = 1, 2          # include/gdf/gdf_amd_ext.h GDF_AMD_ORDER_*
+
+_TORCH_OF_GDF = {1: "int8", 2: "int16", 3: "int32", 4: "int64", 5: "float32", 6: "float64", 7: "int32", 8: "int64", 9: "int64"}
+
+
+def _per_column(value, n):
+    if value is None:
+        return [False] * n
+    if isinstance(value, (bool, np.bool_)):
+        return [bool(value)] * n
+    value = [bool(v) for v in value]
+    if len(value) != n:
+        raise ValueError("one entry per key column")
+    return value
+
+
+def order_by_ex(cols, descending=None, nulls_first=None):
+    """gdf_amd_order_by_ex -> int32 tensor with the stable sorted row permutation of the key Columns, masks honoured.
+    descending / nulls_first: one bool for all columns or one per column (None: ascending / nulls last)."""
+    import torch
+    n = cols[0].size
+    desc, first = _per_column(descending, len(cols)), _per_column(nulls_first, len(cols))
+    flags = (C.c_uint8 * len(cols))(*[(ORDER_DESC if d else 0) | (ORDER_NULLS_FIRST if f else 0) for d, f in zip(desc, first)])
+    out = Column(torch.empty(max(n, 1), dtype=torch.int32, device="cuda"), None, GDF_DTYPES["GDF_INT32"], size=n)
+    libgdf.gdf_amd_order_by_ex(column_array(cols), len(cols), flags, out.ptr)
+    return out.data[:n]
+
+
+def gather(indices, cols):
+    """gdf_amd_gather: the rows of the Columns `cols` that `indices` (an int32 / int64 tensor or Column; -1: a null row) names ->
+    list of Columns that own their memory, each with a mask (ceil(m / 64) * 8 bytes) and an exact null_count; dtype and time
+    unit are the source's."""
+    import torch
+    idx = indices if isinstance(indices, Column) else Column(indices)
+    outs = [gdf_column() for _ in cols]
+    outs_arr = (C.POINTER(gdf_column) * len(cols))(*[C.pointer(o) for o in outs])
+    libgdf.gdf_amd_gather(idx.ptr, len(cols), column_array(list(cols)), outs_arr)
+    res = []
+    for o in outs:
+        m, dtype, nulls, unit = int(o.size), int(o.dtype), int(o.null_count), int(o.dtype_info.time_unit)
+        valid = torch.empty((m + 63) // 64 * 8, dtype=torch.uint8, device="cuda")
+        if m:
+            _hipMemcpyDtoD(valid.data_ptr(), o.valid, valid.numel())
+        if m:
+            data = _take_library_column(o, getattr(torch, _TORCH_OF_GDF[dtype]))      # (frees data and valid)
+        else:
+            data = torch.empty(0, dtype=getattr(torch, _TORCH_OF_GDF[dtype]), device="cuda")
+        res.append(Column(data, valid, dtype, size=m, null_count=nulls, time_unit=unit))
+    return res
+
+
 def hash_rows(cols, hash_func=GDF_HASH_MURMUR3):
     import torch
     n = cols[0].size

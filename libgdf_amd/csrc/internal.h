@@ -52,6 +52,13 @@ gdf_error key_ranges(const KeyTable &t, long long *lo_hi, int windows = 1, int64
 gdf_error radix_sort_pairs_u64(uint64_t *&kin, uint64_t *&kout, uint64_t *&vin, uint64_t *&vout, uint32_t n, uint64_t varying);
 // the same with 32-bit keys (12-byte pairs): a quarter less traffic per pass when the key bits fit
 gdf_error radix_sort_pairs_k32_u64(uint32_t *&kin, uint32_t *&kout, uint64_t *&vin, uint64_t *&vout, uint32_t n, uint64_t varying);
+// the same with (64-bit key, uint32 row number) pairs: the passes of order_rows
+gdf_error radix_sort_pairs_u32(uint64_t *&kin, uint64_t *&kout, uint32_t *&vin, uint32_t *&vout, uint32_t n, uint64_t varying);
+// sort.hip: order_rows' hybrid sort of (image, row) pairs -- the top bits by array passes, the rest in LDS.  *done = false: the shape
+// is not one for it, nothing was touched and the caller runs radix_sort_pairs_u32.  perm64 / perm32: an optional destination of the
+// caller's for the sorted row numbers (size_t / uint32); *perm64_written says whether it was used (vin then holds nothing)
+gdf_error hybrid_sort_pairs(uint64_t *&kin, uint64_t *&kout, uint32_t *&vin, uint32_t *&vout, uint32_t n, uint64_t varying, bool want_keys,
+                            size_t *perm64, bool *perm64_written, bool *done, uint32_t *perm32 = nullptr);
 // sort.hip: SORT-method group-by (op = GbOp of groupby.hip, 5 = COUNT_DISTINCT)
 gdf_error group_by_sort(int ncols, gdf_column **cols, gdf_column *col_agg, gdf_column *out_col_indices,
                         gdf_column **out_col_values, gdf_column *out_col_agg, gdf_context *ctxt, int op);

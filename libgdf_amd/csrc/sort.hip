@@ -393,6 +393,9 @@ gdf_error radix_sort_pairs(K *&kin, K *&kout, V *&vin, V *&vout, uint32_t n, uin
 gdf_error radix_sort_pairs_u64(uint64_t *&kin, uint64_t *&kout, uint64_t *&vin, uint64_t *&vout, uint32_t n, uint64_t varying) {
   return radix_sort_pairs<uint64_t, uint64_t>(kin, kout, vin, vout, n, varying);
 }
+gdf_error radix_sort_pairs_u32(uint64_t *&kin, uint64_t *&kout, uint32_t *&vin, uint32_t *&vout, uint32_t n, uint64_t varying) {
+  return radix_sort_pairs<uint64_t, uint32_t>(kin, kout, vin, vout, n, varying);
+}
 gdf_error radix_sort_pairs_k32_u64(uint32_t *&kin, uint32_t *&kout, uint64_t *&vin, uint64_t *&vout, uint32_t n, uint64_t varying) {
   return radix_sort_pairs<uint32_t, uint64_t>(kin, kout, vin, vout, n, varying);
 }
@@ -645,8 +648,10 @@ __global__ __launch_bounds__(256) void hs_local(HsArgs a, const uint32_t *__rest
 }
 
 // *done = false: the shape is not one for this path (nothing was touched) -- the caller runs radix_sort_pairs
-static gdf_error hybrid_sort_pairs(uint64_t *&kin, uint64_t *&kout, uint32_t *&vin, uint32_t *&vout, uint32_t n, uint64_t varying,
-                                   bool want_keys, size_t *perm64, bool *perm64_written, bool *done) {
+// perm32 (order.hip): the caller's own uint32 destination for the sorted row numbers, written by hs_local in place of vout unless it
+// is hs_local's input -- as perm64, it holds the result only when *perm64_written comes back true, and vin then holds nothing
+gdf_error hybrid_sort_pairs(uint64_t *&kin, uint64_t *&kout, uint32_t *&vin, uint32_t *&vout, uint32_t n, uint64_t varying,
+                            bool want_keys, size_t *perm64, bool *perm64_written, bool *done, uint32_t *perm32) {
   *done = false;
   if (lab::path_on("GDF_SORT_NO_HYBRID") || varying == 0) return GDF_SUCCESS;
   const uint32_t min_rows = (uint32_t)lab::path_int("GDF_HS_MIN_ROWS", 1 << 21);
@@ -682,7 +687,8 @@ static gdf_error hybrid_sort_pairs(uint64_t *&kin, uint64_t *&kout, uint32_t *&v
   GDF_TRY((radix_sort_pairs<uint64_t, uint32_t>(kin, kout, vin, vout, n, varying & top_bits)));
   HIP_TRY(hipMemsetAsync(first, 0, sizeof(uint32_t) * 2 * (size_t)nb, stream0()));
   GDF_LAUNCH("hs_bounds", hs_bounds, dim3(stream_grid(n, 256 * 8)), dim3(256), 0, stream0(), (const uint64_t *)kin, n, shift, tmask, first, last);
-  HsArgs a{kin, vin, want_keys ? kout : nullptr, vout, perm64, lo, shift, varying, (int)lab::path_int("GDF_HS_DBG", 0)};   // (the sorted images leave only for a caller that reads them)
+  uint32_t *const v32 = perm32 && perm32 != vin ? perm32 : vout;
+  HsArgs a{kin, vin, want_keys ? kout : nullptr, v32, perm64, lo, shift, varying, (int)lab::path_int("GDF_HS_DBG", 0)};   // (the sorted images leave only for a caller that reads them)
   GDF_LAUNCH("hs_local", hs_local, dim3(nb / 4), dim3(256), 0, stream0(), a, (const uint32_t *)first, (const uint32_t *)last,
              flags.as<uint32_t>() + 1);
   uint32_t oversize = 0;
@@ -693,7 +699,7 @@ static gdf_error hybrid_sort_pairs(uint64_t *&kin, uint64_t *&kout, uint32_t *&v
   } else {
     std::swap(kin, kout);
     std::swap(vin, vout);
-    if (perm64 && perm64_written) *perm64_written = true;
+    if ((perm64 || v32 == perm32) && perm64_written) *perm64_written = true;
   }
   *done = true;
   return GDF_SUCCESS;

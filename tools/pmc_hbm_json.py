@@ -35,7 +35,7 @@ def main():
     write, _ = collect(sys.argv[2], "WRITE_SIZE")
     kernels = {}
     for k in fetch:
-        if not k.startswith(("jk_", "gj_", "scan_", "gb_", "gbp_", "rs_", "sg_", "hp_", "fj_", "stable_", "part_")):
+        if not k.startswith(("jk_", "gj_", "scan_", "gb_", "gbp_", "rs_", "sg_", "hp_", "fj_", "stable_", "part_", "hs_", "ob_", "ga_")):
             continue
         kernels[k] = {"fetch_kb_reported": fetch[k], "write_kb_reported": write.get(k, 0.0), "launches": nf[k],
                       "hbm_bytes_per_join_corrected": 2.0 * fetch[k] * 1024.0 + write.get(k, 0.0) * 1024.0}
