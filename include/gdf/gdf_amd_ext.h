@@ -2,7 +2,8 @@
  * gdf_amd_ext.h -- exports of libgdf.so that the reference does NOT have.  Nothing here is needed by a
  * caller of the reference API; they exist for measurement (bench.py, tools/), for tests, for the multi-GPU
  * layer (libgdf_amd/multigpu.py), which sits above the unchanged gdf_* ABI, and for what the reference ABI cannot
- * express: a CSV reader over device bytes, ORDER BY over masked columns with a direction per column, a row gather.
+ * express: a CSV reader over device bytes, ORDER BY over masked columns with a direction per column, a row gather, a GROUP BY with
+ * several aggregates whose null keys form groups.
  */
 #ifndef GDF_AMD_EXT_H
 #define GDF_AMD_EXT_H
@@ -325,6 +326,54 @@ gdf_error gdf_amd_order_by_ex(gdf_column **cols, int ncols, const uint8_t *flags
  * Determinism and stream as gdf_amd_order_by_ex.
  */
 gdf_error gdf_amd_gather(gdf_column *indices, int ncols, gdf_column **cols, gdf_column **outs);
+
+/*
+ * gdf_amd_group_by_agg -- GROUP BY over 1 ... 16 key columns with any number of aggregates in ONE call (csrc/groupby_agg.hip):
+ * SELECT k1, k2, SUM(a), AVG(a), MIN(b), COUNT(c), COUNT(*) ... GROUP BY k1, k2 over a table whose columns carry masks, as read_csv
+ * returns it.  The five gdf_group_by_<op> entries stay as they are (one aggregate per call, caller-preallocated outputs of `rows`
+ * elements, a row with a null key dropped by HASH and masks refused by SORT).
+ *
+ *   keys      1 ... 16 columns of equal size `rows`; the dtypes gdf_amd_order_by_ex takes; masks honoured
+ *   values    0 ... 64 columns of that size; masks honoured
+ *   aggs      HOST array of 1 ... 64 requests (column, op): column indexes values[], op is GDF_SUM, GDF_MIN, GDF_MAX, GDF_AVG or
+ *             GDF_COUNT; column == -1 with GDF_COUNT is COUNT(*).  A value column may stand in any number of requests.
+ *   out_keys  nkeys, out_aggs naggs column structs the call fills in, as gdf_amd_gather does: data and valid from rmmAlloc (release
+ *             with gdf_column_free), size G = the number of groups.  EVERY output has a mask of ceil(G / 64) * 8 bytes whose bits
+ *             beyond G are zero and an exact null_count; a null element has data 0.
+ *
+ * Groups       two rows belong to one group when in every key column they are both null, or both valid and equal under
+ *              gdf_order_by's value equality: -0.0 == +0.0, every NaN equals every NaN.  The data under a null bit is never compared.
+ *              Nulls FORM groups: (null, 1), (null, 2) and (1, null) are three groups.  (pandas' dropna: remove the output groups
+ *              whose key masks have a zero bit.)  The groups come out in the order gdf_amd_order_by_ex(keys, flags = NULL) gives
+ *              their rows: ascending, a column's nulls behind its values.
+ * Key outputs  dtype and dtype_info of keys[c]; the element is the bits of the group's FIRST row in input order (which zero, which
+ *              NaN payload); null where the group's key is null.
+ * Aggregates   GDF_SUM    GDF_INT64 for INT8 ... INT64 values (wraps modulo 2^64), GDF_FLOAT64 for FLOAT32 / FLOAT64 (float32 widened
+ *                         before the first add): the sum of the group's valid values; null when the group has none
+ *              GDF_AVG    GDF_FLOAT64: (double)sum / count, sum as under GDF_SUM, count = the valid values; null when there is none
+ *              GDF_MIN / GDF_MAX   dtype and dtype_info of the value column.  Integers signed; floats in gdf_order_by's order, NaN
+ *                         above +inf: MAX is NaN if any valid value is, MIN only if all are (a canonical quiet NaN comes back);
+ *                         of -0.0 and +0.0 either may come back.  Null when the group has no valid value
+ *              GDF_COUNT  GDF_INT64: the valid values of values[column], or the rows of the group for column == -1; never null
+ *              SUM and AVG take INT8 ... FLOAT64 values; MIN and MAX also DATE32, DATE64, TIMESTAMP; COUNT any dtype
+ *              get_column_byte_width knows.
+ * Determinism  a second call on the same input gives bit-identical outputs, float sums included: every fold has a fixed association
+ *              order (which one is the implementation's) and no floating-point atomic takes part.  Runs on the legacy default stream
+ *              and returns after the outputs are written.
+ * Errors       all checked on the host before any device work, out_keys / out_aggs untouched, nothing stays allocated; in this order:
+ *              keys NULL, nkeys <= 0 or a NULL element; nvalues < 0, or nvalues > 0 with values NULL or a NULL element; aggs NULL or
+ *              naggs <= 0; out_keys / out_aggs NULL or a NULL element -> GDF_DATASET_EMPTY; nkeys > 16 -> GDF_JOIN_TOO_MANY_COLUMNS;
+ *              nvalues > 64 or naggs > 64 -> GDF_INVALID_API_CALL; a key or value size other than keys[0]->size ->
+ *              GDF_COLUMN_SIZE_MISMATCH; a key dtype outside the list -> GDF_UNSUPPORTED_DTYPE; then per request in array order: another
+ *              op (GDF_COUNT_DISTINCT too) -> GDF_UNSUPPORTED_METHOD, column outside [-1, nvalues) or -1 without GDF_COUNT ->
+ *              GDF_INVALID_API_CALL, a value dtype the op does not take -> GDF_UNSUPPORTED_DTYPE; rows >= 2^31 - 1 ->
+ *              GDF_COLUMN_SIZE_TOO_BIG; rows > 0 and a key or a referenced value column without data -> GDF_DATASET_EMPTY.
+ *              rows == 0: success without device work, every output of size 0 with data == valid == NULL, null_count 0 and the dtype
+ *              and dtype_info it would have had.
+ */
+typedef struct gdf_amd_agg { int32_t column; int32_t op; } gdf_amd_agg;   /* column: index into values[]; -1 with GDF_COUNT = COUNT(*) */
+gdf_error gdf_amd_group_by_agg(gdf_column **keys, int nkeys, gdf_column **values, int nvalues, const gdf_amd_agg *aggs, int naggs,
+                               gdf_column **out_keys, gdf_column **out_aggs);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

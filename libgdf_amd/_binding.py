@@ -92,6 +92,11 @@ class rmmOptions_t(C.Structure):
     _fields_ = [("allocation_mode", C.c_int), ("initial_pool_size", C.c_size_t), ("enable_logging", C.c_bool)]
 
 
+class gdf_amd_agg(C.Structure):
+    """One request of gdf_amd_group_by_agg (include/gdf/gdf_amd_ext.h): column indexes values[], -1 with GDF_COUNT is COUNT(*)."""
+    _fields_ = [("column", C.c_int32), ("op", C.c_int32)]
+
+
 _COLP = C.POINTER(gdf_column)
 _COLPP = C.POINTER(_COLP)
 _CTXP = C.POINTER(gdf_context)
@@ -195,6 +200,8 @@ _PROTOTYPES = {
     # null-aware ORDER BY and the row gather (csrc/order.hip); flags is a HOST array of bytes
     "gdf_amd_order_by_ex": (None, [_COLPP, C.c_int, C.POINTER(C.c_uint8), _COLP]),
     "gdf_amd_gather": (None, [_COLP, C.c_int, _COLPP, _COLPP]),
+    # GROUP BY with several aggregates over masked columns (csrc/groupby_agg.hip); aggs is a HOST array
+    "gdf_amd_group_by_agg": (None, [_COLPP, C.c_int, _COLPP, C.c_int, C.POINTER(gdf_amd_agg), C.c_int, _COLPP, _COLPP]),
 }
 for _op in ("sum", "product", "min", "max", "sum_squared"):
     for _sfx in (("generic", "f64", "f32") if _op == "sum_squared" else ("generic", "f64", "f32", "i64", "i32", "i8")):

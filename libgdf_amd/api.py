@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from ._binding import (BINARY_OPS, CAST_TARGETS, DATETIME_FIELDS, GDF_UNSUPPORTED_METHOD, MATH_OPS, GDFError, csr_gdf,
-                       csv_read_arg, gdf_column, libgdf, librmm)
+                       csv_read_arg, gdf_amd_agg, gdf_column, libgdf, librmm)
 from .columns import (GDF_DTYPES, GDF_HASH, GDF_HASH_MURMUR3, GDF_SORT, GDF_TO_NP, TIME_UNITS, Column, column_array,
                       new_context)
 
@@ -169,27 +169,46 @@ def order_by_ex(cols, descending=None, nulls_first=None):
     return out.data[:n]
 
 
+def _take_masked_column(o: gdf_column) -> Column:
+    """A column the library allocated WITH a mask of ceil(size / 64) * 8 bytes (gdf_amd_gather, gdf_amd_group_by_agg) -> a Column that
+    owns torch copies of data and mask, with null_count, dtype and time unit; the library's buffers are freed."""
+    import torch
+    m, dtype, nulls, unit = int(o.size), int(o.dtype), int(o.null_count), int(o.dtype_info.time_unit)
+    valid = torch.empty((m + 63) // 64 * 8, dtype=torch.uint8, device="cuda")
+    if m:
+        _hipMemcpyDtoD(valid.data_ptr(), o.valid, valid.numel())
+    if m:
+        data = _take_library_column(o, getattr(torch, _TORCH_OF_GDF[dtype]))      # (frees data and valid)
+    else:
+        data = torch.empty(0, dtype=getattr(torch, _TORCH_OF_GDF[dtype]), device="cuda")
+    return Column(data, valid, dtype, size=m, null_count=nulls, time_unit=unit)
+
+
 def gather(indices, cols):
     """gdf_amd_gather: the rows of the Columns `cols` that `indices` (an int32 / int64 tensor or Column; -1: a null row) names ->
     list of Columns that own their memory, each with a mask (ceil(m / 64) * 8 bytes) and an exact null_count; dtype and time
     unit are the source's."""
-    import torch
     idx = indices if isinstance(indices, Column) else Column(indices)
     outs = [gdf_column() for _ in cols]
     outs_arr = (C.POINTER(gdf_column) * len(cols))(*[C.pointer(o) for o in outs])
     libgdf.gdf_amd_gather(idx.ptr, len(cols), column_array(list(cols)), outs_arr)
-    res = []
-    for o in outs:
-        m, dtype, nulls, unit = int(o.size), int(o.dtype), int(o.null_count), int(o.dtype_info.time_unit)
-        valid = torch.empty((m + 63) // 64 * 8, dtype=torch.uint8, device="cuda")
-        if m:
-            _hipMemcpyDtoD(valid.data_ptr(), o.valid, valid.numel())
-        if m:
-            data = _take_library_column(o, getattr(torch, _TORCH_OF_GDF[dtype]))      # (frees data and valid)
-        else:
-            data = torch.empty(0, dtype=getattr(torch, _TORCH_OF_GDF[dtype]), device="cuda")
-        res.append(Column(data, valid, dtype, size=m, null_count=nulls, time_unit=unit))
-    return res
+    return [_take_masked_column(o) for o in outs]
+
+
+def group_by_agg(keys, values, aggs):
+    """gdf_amd_group_by_agg: GROUP BY the key Columns with several aggregates in one call, masks honoured, null keys forming groups.
+    aggs: list of (index into values or None, "sum" | "min" | "max" | "avg" | "count"); (None, "count") is COUNT(*).
+    -> (list of key Columns, list of aggregate Columns), one row per group in ascending key order with nulls last; every Column owns
+    its memory and carries a mask (ceil(G / 64) * 8 bytes), an exact null_count, its dtype and time unit."""
+    keys, values = list(keys), list(values)
+    reqs = (gdf_amd_agg * max(len(aggs), 1))()
+    for r, (col, op) in zip(reqs, aggs):
+        r.column, r.op = (-1 if col is None else int(col)), _AGG_OPS[op]
+    out_keys, out_aggs = [gdf_column() for _ in keys], [gdf_column() for _ in aggs]
+    ka = (C.POINTER(gdf_column) * len(keys))(*[C.pointer(o) for o in out_keys])
+    aa = (C.POINTER(gdf_column) * max(len(aggs), 1))(*[C.pointer(o) for o in out_aggs])
+    libgdf.gdf_amd_group_by_agg(column_array(keys), len(keys), column_array(values) if values else None, len(values), reqs, len(aggs), ka, aa)
+    return [_take_masked_column(o) for o in out_keys], [_take_masked_column(o) for o in out_aggs]
 
 
 def hash_rows(cols, hash_func=GDF_HASH_MURMUR3):

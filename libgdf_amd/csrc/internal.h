@@ -63,4 +63,40 @@ gdf_error hybrid_sort_pairs(uint64_t *&kin, uint64_t *&kout, uint32_t *&vin, uin
 gdf_error group_by_sort(int ncols, gdf_column **cols, gdf_column *col_agg, gdf_column *out_col_indices,
                         gdf_column **out_col_values, gdf_column *out_col_agg, gdf_context *ctxt, int op);
 
+// order.hip: gdf_amd_order_by_ex behind its argument checks -- the stable permutation of rows [0, n) under (cols, flags) -> dst
+// (n x uint32, DEVICE).  The caller has made gdf_amd_order_by_ex's checks on cols (1 <= ncols <= 16, equal sizes, key dtypes, data
+// pointers) and 0 < n < 2^31 - 1; flags may be null.  Returns after dst is written.  sorted_images (may be null): receives the n sorted
+// 64-bit images when one image holds the whole key -- equal images then mean equal rows, nulls included -- and stays empty otherwise.
+gdf_error order_rows_ex(gdf_column **cols, int ncols, const uint8_t *flags, uint32_t n, uint32_t *dst, DevBuf *sorted_images);
+// order.hip: gdf_amd_gather behind the guard (its own checks included; outs untouched unless it succeeds)
+gdf_error gather_columns(gdf_column *indices, int ncols, gdf_column **cols, gdf_column **outs);
+
+#ifdef __HIPCC__
+// order.hip's value images, shared with groupby_agg.hip.
+// (the same images as sort.hip's ordered_float_bits: -0.0 folded onto +0.0, every NaN behind +inf)
+__device__ __forceinline__ uint64_t ob_float_image_of(uint64_t raw, int kind) {      // raw: the element's storage bits, zero-extended
+  if (kind == K_F32) {
+    uint32_t b = (uint32_t)raw;
+    if ((b << 1) == 0) b = 0;
+    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    return (b >> 31) ? (uint32_t)~b : (b | 0x80000000u);
+  }
+  uint64_t b = raw;
+  if ((b << 1) == 0) b = 0;
+  if ((b & 0x7fffffffffffffffULL) > 0x7ff0000000000000ULL) return ~0ULL;
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
+}
+__device__ __forceinline__ uint64_t ob_float_image(const void *data, int kind, int64_t i) {
+  return ob_float_image_of(kind == K_F32 ? (uint64_t)((const uint32_t *)data)[i] : ((const uint64_t *)data)[i], kind);
+}
+__device__ __forceinline__ uint64_t ob_load_int(const void *data, int kind, int64_t i) {
+  switch (kind) {
+    case K_I8: return (uint64_t)(long long)((const int8_t *)data)[i];
+    case K_I16: return (uint64_t)(long long)((const int16_t *)data)[i];
+    case K_I32: return (uint64_t)(long long)((const int32_t *)data)[i];
+    default: return ((const uint64_t *)data)[i];
+  }
+}
+#endif  // __HIPCC__
+
 }  // namespace gdf_amd

@@ -42,27 +42,7 @@ struct OrdGroup {
   OrdField f[8];
 };
 
-// (the same images as sort.hip's ordered_float_bits: -0.0 folded onto +0.0, every NaN behind +inf)
-__device__ __forceinline__ uint64_t ob_float_image(const void *data, int kind, int64_t i) {
-  if (kind == K_F32) {
-    uint32_t b = ((const uint32_t *)data)[i];
-    if ((b << 1) == 0) b = 0;
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    return (b >> 31) ? (uint32_t)~b : (b | 0x80000000u);
-  }
-  uint64_t b = ((const uint64_t *)data)[i];
-  if ((b << 1) == 0) b = 0;
-  if ((b & 0x7fffffffffffffffULL) > 0x7ff0000000000000ULL) return ~0ULL;
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
-__device__ __forceinline__ uint64_t ob_load_int(const void *data, int kind, int64_t i) {
-  switch (kind) {
-    case K_I8: return (uint64_t)(long long)((const int8_t *)data)[i];
-    case K_I16: return (uint64_t)(long long)((const int16_t *)data)[i];
-    case K_I32: return (uint64_t)(long long)((const int32_t *)data)[i];
-    default: return ((const uint64_t *)data)[i];
-  }
-}
+// (ob_float_image / ob_load_int: internal.h -- groupby_agg.hip compares and folds with the same images)
 __device__ __forceinline__ uint64_t ob_image(const OrdGroup &g, int64_t row) {
   uint64_t k = 0;
   for (int c = 0; c < g.nf; ++c) {
@@ -106,23 +86,12 @@ __global__ __launch_bounds__(256) void ob_make_keys(OrdGroup g, const uint32_t *
 
 static int ob_bit_length(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
 
-static gdf_error order_by_ex(gdf_column **cols, int ncols, const uint8_t *flags, gdf_column *out) {
-  GDF_REQUIRE(cols != nullptr && ncols > 0, GDF_DATASET_EMPTY);
-  for (int c = 0; c < ncols; ++c) GDF_REQUIRE(cols[c] != nullptr, GDF_DATASET_EMPTY);
-  GDF_REQUIRE(ncols <= MAX_KEY_COLS, GDF_JOIN_TOO_MANY_COLUMNS);
-  const gdf_size_type rows = cols[0]->size;
-  for (int c = 0; c < ncols; ++c) GDF_REQUIRE(cols[c]->size == rows, GDF_COLUMN_SIZE_MISMATCH);
-  for (int c = 0; c < ncols; ++c) GDF_REQUIRE(elem_kind(cols[c]->dtype) != K_BAD, GDF_UNSUPPORTED_DTYPE);
-  const uint8_t known = GDF_AMD_ORDER_DESC | GDF_AMD_ORDER_NULLS_FIRST;
-  for (int c = 0; flags && c < ncols; ++c) GDF_REQUIRE((flags[c] & ~known) == 0, GDF_INVALID_API_CALL);
-  GDF_REQUIRE(out != nullptr && out->dtype == GDF_INT32 && out->size == rows, GDF_INVALID_API_CALL);
-  GDF_REQUIRE(rows == 0 || out->data != nullptr, GDF_INVALID_API_CALL);
-  GDF_REQUIRE(out->valid == nullptr, GDF_VALIDITY_UNSUPPORTED);
-  GDF_REQUIRE(rows < (gdf_size_type)0x7fffffff, GDF_COLUMN_SIZE_TOO_BIG);
-  if (rows == 0) return GDF_SUCCESS;
-  for (int c = 0; c < ncols; ++c) GDF_REQUIRE(cols[c]->data != nullptr, GDF_DATASET_EMPTY);
-  const uint32_t n = (uint32_t)rows;
-
+// The stable permutation of rows [0, n) under (cols, flags) -> dst (n x uint32, device).  The arguments are the CHECKED ones of
+// gdf_amd_order_by_ex (1 <= ncols <= 16, equal sizes, key dtypes, data pointers, 0 < n < 2^31 - 1); flags may be null.  Returns after
+// dst is written.  groupby_agg.hip groups on this order; it passes sorted_images, which receives the n sorted 64-bit images when ONE
+// column group holds the whole key: two rows are then equal on every key column (both null, or equal values) exactly when their images
+// are, so the group boundaries need no gather.  With more than one column group sorted_images stays empty.
+gdf_error order_rows_ex(gdf_column **cols, int ncols, const uint8_t *flags, uint32_t n, uint32_t *dst, DevBuf *sorted_images) {
   KeyTable t;
   GDF_TRY(make_key_table(cols, ncols, &t));
   std::vector<long long> lo_hi(2 * (size_t)ncols);
@@ -193,11 +162,11 @@ static gdf_error order_by_ex(gdf_column **cols, int ncols, const uint8_t *flags,
   RMM_TRY(kb.alloc(sizeof(uint64_t) * (size_t)n));
   RMM_TRY(vb.alloc(sizeof(uint32_t) * (size_t)n));
   RMM_TRY(vary.alloc(sizeof(unsigned long long)));
-  uint32_t *const dst = static_cast<uint32_t *>(out->data);
   uint64_t *kin = ka.as<uint64_t>(), *kout = kb.as<uint64_t>();
   uint32_t *vin = vb.as<uint32_t>(), *vout = dst;
   const int sgrid = stream_grid(n, 256 * 8);
   bool have_perm = false, written = false;
+  const bool want_images = sorted_images != nullptr && groups.size() == 1;
   for (size_t gi = 0; gi < groups.size(); ++gi) {
     const bool last_group = gi + 1 == groups.size();
     HIP_TRY(hipMemsetAsync(vary.p, 0, sizeof(unsigned long long), stream0()));
@@ -209,13 +178,35 @@ static gdf_error order_by_ex(gdf_column **cols, int ncols, const uint8_t *flags,
     HIP_TRY(hipStreamSynchronize(stream0()));
     bool hybrid = false;
     // (the last group's hs_local writes the row numbers straight into the caller's column unless that column is its input)
-    GDF_TRY(hybrid_sort_pairs(kin, kout, vin, vout, n, varying, false, nullptr, &written, &hybrid, last_group ? dst : nullptr));
+    GDF_TRY(hybrid_sort_pairs(kin, kout, vin, vout, n, varying, want_images, nullptr, &written, &hybrid, last_group ? dst : nullptr));
     if (!hybrid) GDF_TRY(radix_sort_pairs_u32(kin, kout, vin, vout, n, varying));
   }
   HIP_CHECK_LAST();
   if (!written && vin != dst) HIP_TRY(hipMemcpyAsync(dst, vin, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, stream0()));
   HIP_TRY(hipStreamSynchronize(stream0()));
+  if (want_images) {
+    sorted_images->reset();
+    sorted_images->p = (kin == ka.as<uint64_t>() ? ka : kb).release();
+  }
   return GDF_SUCCESS;
+}
+
+static gdf_error order_by_ex(gdf_column **cols, int ncols, const uint8_t *flags, gdf_column *out) {
+  GDF_REQUIRE(cols != nullptr && ncols > 0, GDF_DATASET_EMPTY);
+  for (int c = 0; c < ncols; ++c) GDF_REQUIRE(cols[c] != nullptr, GDF_DATASET_EMPTY);
+  GDF_REQUIRE(ncols <= MAX_KEY_COLS, GDF_JOIN_TOO_MANY_COLUMNS);
+  const gdf_size_type rows = cols[0]->size;
+  for (int c = 0; c < ncols; ++c) GDF_REQUIRE(cols[c]->size == rows, GDF_COLUMN_SIZE_MISMATCH);
+  for (int c = 0; c < ncols; ++c) GDF_REQUIRE(elem_kind(cols[c]->dtype) != K_BAD, GDF_UNSUPPORTED_DTYPE);
+  const uint8_t known = GDF_AMD_ORDER_DESC | GDF_AMD_ORDER_NULLS_FIRST;
+  for (int c = 0; flags && c < ncols; ++c) GDF_REQUIRE((flags[c] & ~known) == 0, GDF_INVALID_API_CALL);
+  GDF_REQUIRE(out != nullptr && out->dtype == GDF_INT32 && out->size == rows, GDF_INVALID_API_CALL);
+  GDF_REQUIRE(rows == 0 || out->data != nullptr, GDF_INVALID_API_CALL);
+  GDF_REQUIRE(out->valid == nullptr, GDF_VALIDITY_UNSUPPORTED);
+  GDF_REQUIRE(rows < (gdf_size_type)0x7fffffff, GDF_COLUMN_SIZE_TOO_BIG);
+  if (rows == 0) return GDF_SUCCESS;
+  for (int c = 0; c < ncols; ++c) GDF_REQUIRE(cols[c]->data != nullptr, GDF_DATASET_EMPTY);
+  return order_rows_ex(cols, ncols, flags, (uint32_t)rows, static_cast<uint32_t *>(out->data), nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -299,7 +290,7 @@ __global__ __launch_bounds__(GA_THREADS) void ga_gather(const I *__restrict__ id
   }
 }
 
-static gdf_error gather(gdf_column *indices, int ncols, gdf_column **cols, gdf_column **outs) {
+gdf_error gather_columns(gdf_column *indices, int ncols, gdf_column **cols, gdf_column **outs) {
   GDF_REQUIRE(indices != nullptr && cols != nullptr && outs != nullptr && ncols > 0, GDF_DATASET_EMPTY);
   for (int c = 0; c < ncols; ++c) GDF_REQUIRE(cols[c] != nullptr && outs[c] != nullptr, GDF_DATASET_EMPTY);
   const gdf_size_type rows_u = cols[0]->size;
@@ -366,7 +357,7 @@ gdf_error gdf_amd_order_by_ex(gdf_column **cols, int ncols, const uint8_t *flags
 }
 
 gdf_error gdf_amd_gather(gdf_column *indices, int ncols, gdf_column **cols, gdf_column **outs) {
-  return gdf_amd::guarded([&]() -> gdf_error { return gdf_amd::gather(indices, ncols, cols, outs); });
+  return gdf_amd::guarded([&]() -> gdf_error { return gdf_amd::gather_columns(indices, ncols, cols, outs); });
 }
 
 }  // extern "C"
