@@ -375,6 +375,28 @@ typedef struct gdf_amd_agg { int32_t column; int32_t op; } gdf_amd_agg;   /* col
 gdf_error gdf_amd_group_by_agg(gdf_column **keys, int nkeys, gdf_column **values, int nvalues, const gdf_amd_agg *aggs, int naggs,
                                gdf_column **out_keys, gdf_column **out_aggs);
 
+/*
+ * gdf_amd_top_k -- ORDER BY ... LIMIT k OFFSET offset without sorting the table (csrc/topk.hip): a radix selection over a 64-bit
+ * image of the key, then a sort of the few rows that can make the cut.
+ *
+ *   cols, flags  exactly as for gdf_amd_order_by_ex: 1 ... 16 key columns, the same dtypes, masks honoured at any alignment,
+ *                null_count not consulted, the data under a null bit never loaded for comparison; flags a HOST array or NULL
+ *   k, offset    the LIMIT and the OFFSET; with rows = cols[0]->size, m = max(0, min(k, rows - offset)) rows come back
+ *   out_indices  caller-preallocated GDF_INT32 column without a mask, size == m (the caller knows rows, k and offset)
+ *
+ * Result       let P be the permutation gdf_amd_order_by_ex(cols, ncols, flags, ...) writes for the same arguments:
+ *              out_indices[i] = P[offset + i] for 0 <= i < m, element for element.  Value order, null placement, DESC, NaN, +-0.0
+ *              and stability are therefore gdf_amd_order_by_ex's: among rows equal on every key column the lower row number comes
+ *              first, and it is also the one that makes the cut.  Nothing outside the first m elements is written.
+ * Errors       all checked on the host before any device work, out_indices untouched; in this order: gdf_amd_order_by_ex's checks
+ *              on cols, ncols, sizes, dtypes and flags, with its codes; k < 0 or offset < 0 -> GDF_INVALID_API_CALL; out_indices
+ *              NULL, not GDF_INT32, size != m, or data == NULL with m > 0 -> GDF_INVALID_API_CALL; out_indices with a mask ->
+ *              GDF_VALIDITY_UNSUPPORTED; rows >= 2^31 - 1 -> GDF_COLUMN_SIZE_TOO_BIG; m > 0 and a key column without data ->
+ *              GDF_DATASET_EMPTY.  m == 0 (k == 0, rows == 0 or offset >= rows): success without device work.
+ * Determinism and stream as gdf_amd_order_by_ex.
+ */
+gdf_error gdf_amd_top_k(gdf_column **cols, int ncols, const uint8_t *flags, int64_t k, int64_t offset, gdf_column *out_indices);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

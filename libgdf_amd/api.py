@@ -169,6 +169,20 @@ def order_by_ex(cols, descending=None, nulls_first=None):
     return out.data[:n]
 
 
+def top_k(cols, k, descending=None, nulls_first=None, offset=0):
+    """gdf_amd_top_k -> int32 tensor with rows [offset, offset + k) of order_by_ex's permutation (fewer when the table ends first),
+    found by a selection instead of a sort of the whole table.  descending / nulls_first as for order_by_ex; the result chains
+    into gather: ``gather(top_k(keys, 100, descending=True), table)`` is ORDER BY ... DESC LIMIT 100."""
+    import torch
+    n, k, offset = cols[0].size, int(k), int(offset)
+    desc, first = _per_column(descending, len(cols)), _per_column(nulls_first, len(cols))
+    flags = (C.c_uint8 * len(cols))(*[(ORDER_DESC if d else 0) | (ORDER_NULLS_FIRST if f else 0) for d, f in zip(desc, first)])
+    m = max(0, min(k, n - offset)) if k >= 0 and offset >= 0 else 0      # (a negative k / offset is the library's error to report)
+    out = Column(torch.empty(max(m, 1), dtype=torch.int32, device="cuda"), None, GDF_DTYPES["GDF_INT32"], size=m)
+    libgdf.gdf_amd_top_k(column_array(cols), len(cols), flags, k, offset, out.ptr)
+    return out.data[:m]
+
+
 def _take_masked_column(o: gdf_column) -> Column:
     """A column the library allocated WITH a mask of ceil(size / 64) * 8 bytes (gdf_amd_gather, gdf_amd_group_by_agg) -> a Column that
     owns torch copies of data and mask, with null_count, dtype and time unit; the library's buffers are freed."""
