@@ -3,7 +3,7 @@
  * caller of the reference API; they exist for measurement (bench.py, tools/), for tests, for the multi-GPU
  * layer (libgdf_amd/multigpu.py), which sits above the unchanged gdf_* ABI, and for what the reference ABI cannot
  * express: a CSV reader over device bytes, ORDER BY over masked columns with a direction per column, a row gather, a GROUP BY with
- * several aggregates whose null keys form groups.
+ * several aggregates whose null keys form groups, ORDER BY ... LIMIT k by selection, EXISTS / NOT EXISTS (semi and anti join).
  */
 #ifndef GDF_AMD_EXT_H
 #define GDF_AMD_EXT_H
@@ -396,6 +396,40 @@ gdf_error gdf_amd_group_by_agg(gdf_column **keys, int nkeys, gdf_column **values
  * Determinism and stream as gdf_amd_order_by_ex.
  */
 gdf_error gdf_amd_top_k(gdf_column **cols, int ncols, const uint8_t *flags, int64_t k, int64_t offset, gdf_column *out_indices);
+
+/*
+ * gdf_amd_semi_join -- SELECT ... FROM L WHERE [NOT] EXISTS (SELECT 1 FROM R WHERE L.k1 = R.k1 AND L.k2 = R.k2 ...): the row numbers
+ * of the left rows that have (GDF_AMD_SEMI_ANTI: have not) a partner among the right rows (csrc/semijoin.hip).  pandas' isin over
+ * several columns, merge(how = "leftsemi" / "leftanti").  At most 4 bytes come back per left row however often the right keys repeat.
+ *
+ *   left_cols, right_cols   ncols (1 ... 16) key columns each, sizes equal within a side; the dtypes gdf_amd_order_by_ex takes, with
+ *                           left_cols[c]->dtype == right_cols[c]->dtype (dtype_info is not consulted, as in the joins).  Masks are
+ *                           honoured at any byte alignment, null_count is not consulted, mask bits beyond size are ignored, and the
+ *                           data under a null bit is never loaded for comparison.
+ *   flags                   GDF_AMD_SEMI_ANTI | GDF_AMD_SEMI_NULLS_EQUAL, or 0
+ *   out_indices             filled in by the call, as the joins fill in their index columns: GDF_INT32, data from rmmAlloc (release
+ *                           with gdf_column_free), valid == NULL, null_count == 0, size == m.  m == 0: size 0 and data == NULL.
+ *
+ * Match        a left row has a partner when some right row agrees with it in every key column.  Values agree exactly as in
+ *              gdf_inner_join: integers by value, floats by ==, so -0.0 == +0.0 and a NaN equals nothing, itself included, under
+ *              either flag.  Without NULLS_EQUAL a row with a null in any key column has no partner and is no partner (the joins'
+ *              rule).  With NULLS_EQUAL two elements of a column also agree when both are null (IS NOT DISTINCT FROM); a null never
+ *              agrees with a value.  Consequence: ANTI without NULLS_EQUAL RETURNS the left rows with a null key -- that is NOT EXISTS,
+ *              not NOT IN.
+ * Result       the row numbers of the qualifying left rows in ASCENDING order, each once: gdf_amd_gather(out_indices, L ...) is the
+ *              filtered table in input order.  A right side without rows gives nothing for SEMI and every left row for ANTI.
+ * Determinism and stream as gdf_amd_order_by_ex: a second call is bit-identical; the call runs on the legacy default stream and
+ *              returns after the output is written.
+ * Errors       all checked on the host before any device work, out_indices untouched, nothing stays allocated; in this order:
+ *              left_cols / right_cols / out_indices NULL, ncols <= 0 or a NULL element -> GDF_DATASET_EMPTY; ncols > 16 ->
+ *              GDF_JOIN_TOO_MANY_COLUMNS; sizes differ within a side -> GDF_COLUMN_SIZE_MISMATCH; a dtype outside the list (either
+ *              side) -> GDF_UNSUPPORTED_DTYPE; left / right dtype of a column differ -> GDF_JOIN_DTYPE_MISMATCH; flag bits other than
+ *              the two -> GDF_INVALID_API_CALL; either side has >= 2^31 - 1 rows -> GDF_COLUMN_SIZE_TOO_BIG; a column of a side that
+ *              has rows, with data == NULL -> GDF_DATASET_EMPTY.
+ */
+#define GDF_AMD_SEMI_ANTI        1u   /* return the left rows WITHOUT a partner (NOT EXISTS)            */
+#define GDF_AMD_SEMI_NULLS_EQUAL 2u   /* a null key equals a null key (IS NOT DISTINCT FROM)             */
+gdf_error gdf_amd_semi_join(gdf_column **left_cols, gdf_column **right_cols, int ncols, uint32_t flags, gdf_column *out_indices);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -202,6 +202,8 @@ _PROTOTYPES = {
     "gdf_amd_gather": (None, [_COLP, C.c_int, _COLPP, _COLPP]),
     # ORDER BY ... LIMIT k OFFSET offset by radix selection (csrc/topk.hip)
     "gdf_amd_top_k": (None, [_COLPP, C.c_int, C.POINTER(C.c_uint8), C.c_int64, C.c_int64, _COLP]),
+    # EXISTS / NOT EXISTS over masked key columns (csrc/semijoin.hip); out_indices is filled in by the library
+    "gdf_amd_semi_join": (None, [_COLPP, _COLPP, C.c_int, C.c_uint32, _COLP]),
     # GROUP BY with several aggregates over masked columns (csrc/groupby_agg.hip); aggs is a HOST array
     "gdf_amd_group_by_agg": (None, [_COLPP, C.c_int, _COLPP, C.c_int, C.POINTER(gdf_amd_agg), C.c_int, _COLPP, _COLPP]),
 }

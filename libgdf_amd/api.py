@@ -183,6 +183,23 @@ def top_k(cols, k, descending=None, nulls_first=None, offset=0):
     return out.data[:m]
 
 
+SEMI_ANTI, SEMI_NULLS_EQUAL = 1, 2           # include/gdf/gdf_amd_ext.h GDF_AMD_SEMI_*
+
+
+def semi_join(left, right, anti=False, nulls_equal=False):
+    """gdf_amd_semi_join -> int32 tensor with the ascending row numbers of the rows of `left` (a list of key Columns) that have
+    (anti: have not) a partner among the rows of `right`: WHERE [NOT] EXISTS.  nulls_equal: a null key equals a null key.  The
+    library allocates the result; it is copied into a torch tensor and released, as join(copy=True) does.  The result chains into
+    gather: ``gather(semi_join(lkeys, rkeys), table)`` is the filtered table in input order."""
+    import torch
+    if len(left) != len(right):
+        raise ValueError("one right key column per left key column")
+    out = gdf_column()
+    flags = (SEMI_ANTI if anti else 0) | (SEMI_NULLS_EQUAL if nulls_equal else 0)
+    libgdf.gdf_amd_semi_join(column_array(list(left)), column_array(list(right)), len(left), flags, C.byref(out))
+    return _take_library_column(out, torch.int32)
+
+
 def _take_masked_column(o: gdf_column) -> Column:
     """A column the library allocated WITH a mask of ceil(size / 64) * 8 bytes (gdf_amd_gather, gdf_amd_group_by_agg) -> a Column that
     owns torch copies of data and mask, with null_count, dtype and time unit; the library's buffers are freed."""
